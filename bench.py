@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- SSFM steps/s on MI355X for BASELINE.json's configurations.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5] [--dump-outputs DIR]
+
+--dump-outputs DIR: the output field of every unit after the K timed steps, as DIR/unit<u>.npy (float64 / float32 [real, imag]
+pairs; at most 64 MB in all, a fixed seeded sample of sample positions beyond that -- dump_outputs).  The inputs are seeded: the
+same arguments give the same inputs, so two builds can be compared output for output.
 
 One "step" = one pass of `while z_current < Lspan` (reference optic/models/channels.py:387; the inner `for` of
 ssfm, :219).  The timed region runs EXACTLY K steps per unit with every input already resident in HBM (uploads
@@ -324,6 +328,8 @@ def measure(env, cfg, m):
         outs[u] = o
     d2h_ms = (time.perf_counter() - t_d2h0) * 1e3
     d2h_bytes = sum(o.nbytes for o in outs.values())
+    if getattr(m, "dump_outputs", None):
+        dump_outputs(m.dump_outputs, outs, U)
     xfer = np.array([[h2d_ms, d2h_ms, dt_local * 1e3, float(h2d_bytes), float(d2h_bytes)]])
     xfer_all = comm.allgather(xfer)[:, 0, :] if comm is not None else xfer
     per = max(len(mgpu.shard_range(U, world, r)) for r in range(world))
@@ -531,6 +537,27 @@ def measure(env, cfg, m):
     return rec, ok
 
 
+DUMP_LIMIT_BYTES = 64_000_000                                   # all of DIR, .npy headers included
+
+
+def dump_outputs(d, outs, n_units, seed=4242):
+    """--dump-outputs DIR: what the timed path returned in its last step, one DIR/unit<u>.npy per unit of this rank: the (rows, N)
+    complex field as float64 / float32 (rows, N, 2) pairs [real, imag].  Everything when all n_units fit in 64 MB; otherwise the
+    same fixed, seeded, sorted sample of sample positions in every unit (DIR/sample_index.npy, float64), sized to the budget."""
+    os.makedirs(d, exist_ok=True)
+    o0 = next(iter(outs.values()))
+    rows, N = o0.shape
+    per_sample = rows * o0.itemsize                             # bytes of one sample position (all rows, real + imaginary)
+    keep = min(N, (DUMP_LIMIT_BYTES - 4096 * (n_units + 1)) // (per_sample * max(1, n_units) + 8))
+    idx = None
+    if keep < N:
+        idx = np.sort(np.random.default_rng(seed).choice(N, size=keep, replace=False))
+        np.save(os.path.join(d, "sample_index.npy"), idx.astype(np.float64))
+    for u, o in outs.items():
+        a = o if idx is None else o[:, idx]
+        np.save(os.path.join(d, "unit%d.npy" % u), np.ascontiguousarray(a).view(a.real.dtype).reshape(a.shape + (2,)))
+
+
 def also_configs(env, args):
     """The other single-GPU configurations BASELINE.json names, measured in the same run after the headline (VERDICT round 3,
     item 3): each with its own short parity gate, reported under one extra key.  Budget: about a minute."""
@@ -539,6 +566,7 @@ def also_configs(env, args):
     def leg(key, cfg, **kw):
         m = argparse.Namespace(**vars(args))
         m.nfields, m.parity, m.log2n, m.prec, m.cpu_steps, m.no_kernel_times = 1, "oracle", 0, "", 0, False
+        m.dump_outputs = None                                    # (--dump-outputs: the headline configuration only)
         for k, v in kw.items():
             setattr(m, k, v)
         t0 = time.perf_counter()
@@ -768,6 +796,8 @@ def main():
     ap.add_argument("--no-also", action="store_true", help="headline configuration only (no 'also' legs)")
     ap.add_argument("--parity", default="", help="parity leg: oracle (default) | fixture_cfg3 | fixture_units | none")
     ap.add_argument("--notebook", action="store_true", help="only the reference notebook's benchmark (notebook_leg), as one JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed (every unit's output field) as DIR/unit<u>.npy")
     args = ap.parse_args()
 
     if args.notebook:
