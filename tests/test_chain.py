@@ -60,7 +60,10 @@ def check_against_reference(o, d, cfg, tol=1e-9):
     dd = int(cfg["d"])
     get = lambda x: x.get() if hasattr(x, "get") else np.asarray(x)
     assert np.array_equal(o["symb"][:64], d["symb_head"])
-    assert np.max(np.abs(projection(o["symb"].reshape(len(o["symb"]), -1)) - d["symb_proj"])) == 0
+    # (the projection is a BLAS product whose summation order follows the host's thread count: equal symbols give 0 with one thread
+    #  and a few 1e-13 with sixteen, one differing symbol gives ~0.5)
+    symb = o["symb"].reshape(len(o["symb"]), -1)
+    assert np.max(np.abs(projection(symb) - d["symb_proj"])) <= 1e-12 * np.sqrt(np.sum(np.abs(symb) ** 2))
     worst = {}
     for k in ("tx", "ch", "rx", "mf"):
         a = get(o[k])

@@ -221,14 +221,16 @@ def test_ssfm_and_linear_channel_on_the_mixed_radix_column_stage():
 
 
 def test_forcing_a_radix_2n_length_onto_the_mixed_columns_gives_the_same_field(monkeypatch):
-    """12 000 = 2^5 x 375 runs on the radix-2^n columns; forced onto the mixed-radix column stage (experiment knob SSF_MIX2, read by
-    the emulator's experiment build) both pipelines must agree with the oracle and with each other to rounding."""
-    N = 12000
+    """48 000 = 2^7 x 375 runs on the radix-2^n columns (k_col_ragged: a length needs seven factors of two to stay there, 12 000 =
+    2^5 x 375 already takes the mixed-radix columns by itself); forced onto the mixed-radix column stage (experiment knob SSF_MIX2,
+    read by the emulator's experiment build) both pipelines must agree with the oracle and with each other to rounding."""
+    N = 48000
     E = synth_field(N, 2, 61, 8.4)
     cfg = dict(MK, nlprMethod=False, amp="ideal", saveSpanN=[])
+    assert _mix2(N) is None
     a, ia = eb.run("manakovSSF", E, cfg)
     monkeypatch.setenv("SSF_MIX2", "125,8")
-    assert _mix2(N) == (125, 96, 8)
+    assert _mix2(N) == (125, 384, 8)
     b, ib = eb.run("manakovSSF", E, cfg)
     ref = orc.manakovSSF(E, bag(orc.parameters, **cfg))
     assert rel_l2(a.T, ref) <= 1e-11 and rel_l2(b.T, ref) <= 1e-11 and rel_l2(a, b) <= 1e-12
