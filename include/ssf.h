@@ -484,6 +484,54 @@ typedef struct {
 int  ssf_wdm_tx(int device, const ssf_tx_params *params, const void *symbols, const double *taps, const double *phi,
                 const double *amp, const double *deltaF, void *sig_out, double *power_out);
 
+/* ---- link metrics: BER, SER, SNR, GMI, NGMI, MI and EVM of received against transmitted symbols, evaluated on the device
+ * (optic/comm/metrics.py:111-195 fastBERcalc, 329-426 monteCarloGMI, 429-547 monteCarloMI, 572-637 calcEVM).  One call
+ * normalises once and reads the symbols once per pass (statistics, decisions, soft demapping); `want` selects what is computed,
+ * and a value is the same whatever else is asked for with it.  Sums are reduced in a fixed order: results repeat bit for bit.
+ *   rx, tx      (n, nModes) row-major -- or (nModes, n) with transposed = 1 -- of `dtype`, host or device; never written
+ *   const_raw   M (re, im) pairs: the Gray-ordered constellation as grayMapping stores it (single precision, widened)
+ *   const_norm  M (re, im) pairs: const_raw / sqrt(Es) in double precision; with SSF_METRICS_EVM_BLIND the single-precision
+ *               pnorm(table) the reference decides against
+ *   px          M prior probabilities, NULL = uniform
+ *   evm_w32     SSF_METRICS_EVM_BLIND only: float32 |c_m|^2 of that table (the reference averages it in float32)
+ *   out         nModes results, host
+ * Rows [discard, n - discard) are evaluated.  M is a power of two, 2 .. 1024; nModes <= 64.  SSF_METRICS_EVM_BLIND stands
+ * alone and takes tx = NULL; every other selection needs tx. */
+enum ssf_metrics_dtype { SSF_M_C128 = 0, SSF_M_C64 = 1, SSF_M_F64 = 2, SSF_M_F32 = 3 };
+enum ssf_metrics_want {
+    SSF_METRICS_BER = 1,          /* BER, SER, SNR and the error counts */
+    SSF_METRICS_GMI = 2,          /* GMI, NGMI */
+    SSF_METRICS_MI = 4,
+    SSF_METRICS_EVM = 8,          /* data-aided */
+    SSF_METRICS_EVM_BLIND = 16
+};
+typedef struct {
+    int64_t n;                    /* symbols per mode */
+    int64_t discard;
+    int32_t nModes, M;
+    int32_t dtype;                /* ssf_metrics_dtype of rx and tx */
+    int32_t transposed;
+    int32_t rotate;               /* 1 for 'qam' / 'psk': rx is rotated by mean(tx / rx) */
+    int32_t want;
+    double  Es;                   /* sum |const_raw|^2 px */
+    double  H;                    /* source entropy, bits */
+} ssf_metrics_params;
+typedef struct {
+    double  BER, SER, SNR, GMI, NGMI, MI, EVM;
+    int64_t bit_errors, symbol_errors, n;
+} ssf_metrics_result;
+int  ssf_metrics(int device, const ssf_metrics_params *params, const void *rx, const void *tx, const double *const_raw,
+                 const double *const_norm, const double *px, const float *evm_w32, ssf_metrics_result *out);
+/* y = x / sqrt(mean |x|^2) over all `count` values (optic/dsp/core.py:701-717); y is complex128 for a complex dtype, float64
+ * otherwise; x and y host or device */
+int  ssf_pnorm(int device, int64_t count, int32_t dtype, const void *x, void *y);
+/* out = sum |x|^2 / rows: the sum over the columns of their mean power (optic/dsp/core.py:69-85) */
+int  ssf_signal_power(int device, int64_t count, int64_t rows, int32_t dtype, const void *x, double *out);
+/* minimum-distance decisions of `count` symbols against const_raw, log2(M) bits each, most significant first
+ * (optic/comm/modulation.py:369-408); bits_out: count * log2(M) int32, host or device */
+int  ssf_demodulate(int device, int64_t count, int32_t dtype, int32_t M, const double *const_raw, const void *symb,
+                    int32_t *bits_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,22 @@ class TxParams(C.Structure):
                 ("pn_sigma", C.c_double), ("pn_seed", C.c_uint64), ("phi_rows", C.c_int32), ("reserved", C.c_int32)]
 
 
+class MetricsParams(C.Structure):
+    """ssf_metrics_params (include/ssf.h)."""
+    _fields_ = [("n", C.c_int64), ("discard", C.c_int64), ("nModes", C.c_int32), ("M", C.c_int32), ("dtype", C.c_int32),
+                ("transposed", C.c_int32), ("rotate", C.c_int32), ("want", C.c_int32), ("Es", C.c_double), ("H", C.c_double)]
+
+
+class MetricsResult(C.Structure):
+    """ssf_metrics_result (include/ssf.h): one per mode."""
+    _fields_ = [("BER", C.c_double), ("SER", C.c_double), ("SNR", C.c_double), ("GMI", C.c_double), ("NGMI", C.c_double),
+                ("MI", C.c_double), ("EVM", C.c_double), ("bit_errors", C.c_int64), ("symbol_errors", C.c_int64), ("n", C.c_int64)]
+
+
+METRICS_DTYPES = {"complex128": 0, "complex64": 1, "float64": 2, "float32": 3}              # ssf_metrics_dtype
+METRICS_BER, METRICS_GMI, METRICS_MI, METRICS_EVM, METRICS_EVM_BLIND = 1, 2, 4, 8, 16       # ssf_metrics_want
+
+
 class DeviceInfo(C.Structure):
     _fields_ = [("name", C.c_char * 128), ("arch", C.c_char * 32), ("compute_units", C.c_int32),
                 ("reserved", C.c_int32), ("total_mem_bytes", C.c_int64), ("lds_per_block_bytes", C.c_int64)]
@@ -127,6 +143,11 @@ SYMBOLS = {
                                C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "ssf_wdm_tx": (C.c_int, [C.c_int, C.POINTER(TxParams), C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_double)]),
+    "ssf_metrics": (C.c_int, [C.c_int, C.POINTER(MetricsParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(MetricsResult)]),
+    "ssf_pnorm": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ssf_signal_power": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
+    "ssf_demodulate": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "ssf_device_copy_bandwidth": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_linear_channel": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p]),

@@ -672,4 +672,57 @@ int ssf_wdm_tx(int device, const ssf_tx_params *params, const void *symbols, con
     return rc ? set_err(rc, "ssf_wdm_tx: " + err) : SSF_OK;
 }
 
+// ---- link metrics (engine_metrics.hip): every check comes before the first allocation or launch
+static bool metrics_bad_M(int32_t M) { return M < 2 || M > 1024 || (M & (M - 1)) != 0; }
+static bool metrics_bad_dtype(int32_t d) { return d < SSF_M_C128 || d > SSF_M_F32; }
+
+int ssf_metrics(int device, const ssf_metrics_params *p, const void *rx, const void *tx, const double *const_raw,
+                const double *const_norm, const double *px, const float *evm_w32, ssf_metrics_result *out) {
+    if (!p || !rx || !const_norm || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: NULL argument");
+    if (metrics_bad_M(p->M)) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: M must be a power of two, 2 .. 1024");
+    if (metrics_bad_dtype(p->dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: bad dtype");
+    if (p->nModes < 1 || p->nModes > 64) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: nModes must be 1 .. 64");
+    if (p->n < 1 || p->discard < 0 || 2 * p->discard >= p->n) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: no symbols left to evaluate");
+    const int32_t all = SSF_METRICS_BER | SSF_METRICS_GMI | SSF_METRICS_MI | SSF_METRICS_EVM | SSF_METRICS_EVM_BLIND;
+    if (p->want == 0 || (p->want & ~all)) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: bad selection");
+    if (p->want & SSF_METRICS_EVM_BLIND) {
+        if (p->want != SSF_METRICS_EVM_BLIND || tx || !evm_w32)
+            return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: the blind EVM stands alone, takes no tx and needs evm_w32");
+    } else {
+        if (!tx || !const_raw) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: tx or const_raw is NULL");
+        if (!(p->Es > 0) || !(p->H > 0)) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: Es and H must be positive");
+    }
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::metrics_run(device, p, rx, tx, const_raw, const_norm, px, evm_w32, out, &err);
+    return rc ? set_err(rc, "ssf_metrics: " + err) : SSF_OK;
+}
+
+int ssf_pnorm(int device, int64_t count, int32_t dtype, const void *x, void *y) {
+    if (!x || !y || count < 1 || metrics_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_pnorm: bad argument");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::metrics_pnorm(device, count, dtype, x, y, &err);
+    return rc ? set_err(rc, "ssf_pnorm: " + err) : SSF_OK;
+}
+
+int ssf_signal_power(int device, int64_t count, int64_t rows, int32_t dtype, const void *x, double *out) {
+    if (!x || !out || count < 1 || rows < 1 || count % rows || metrics_bad_dtype(dtype))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_signal_power: bad argument");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::metrics_power(device, count, rows, dtype, x, out, &err);
+    return rc ? set_err(rc, "ssf_signal_power: " + err) : SSF_OK;
+}
+
+int ssf_demodulate(int device, int64_t count, int32_t dtype, int32_t M, const double *const_raw, const void *symb,
+                   int32_t *bits_out) {
+    if (!const_raw || !symb || !bits_out || count < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_demodulate: bad argument");
+    if (metrics_bad_M(M) || metrics_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_demodulate: bad M or dtype");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::metrics_demod(device, count, dtype, M, const_raw, symb, bits_out, &err);
+    return rc ? set_err(rc, "ssf_demodulate: " + err) : SSF_OK;
+}
+
 }  // extern "C"

@@ -146,6 +146,13 @@ int tx_wdm(int device, const ssf_tx_params *p, const void *symbols, const double
            const double *deltaF, void *out, double *power_out, std::string *err);
 int rx_decimate(int device, int64_t N, int ncols, int SpSin, int decFactor, const void *in, void *out, int32_t *sampDelay,
                 std::string *err);
+// engine_metrics.hip (arguments already checked by ssf_api.hip)
+int metrics_run(int device, const ssf_metrics_params *p, const void *rx, const void *tx, const double *const_raw,
+                const double *const_norm, const double *px, const float *evm_w32, ssf_metrics_result *out, std::string *err);
+int metrics_pnorm(int device, int64_t count, int dtype, const void *x, void *y, std::string *err);
+int metrics_power(int device, int64_t count, int64_t rows, int dtype, const void *x, double *out, std::string *err);
+int metrics_demod(int device, int64_t count, int dtype, int M, const double *const_raw, const void *symb, int32_t *bits_out,
+                  std::string *err);
 
 inline int fail(ssf_plan *p, int code, const std::string &msg) {
     if (p) p->err = msg;
