@@ -532,6 +532,39 @@ int  ssf_signal_power(int device, int64_t count, int64_t rows, int32_t dtype, co
 int  ssf_demodulate(int device, int64_t count, int32_t dtype, int32_t M, const double *const_raw, const void *symb,
                     int32_t *bits_out);
 
+/* ---- carrier phase recovery on the device: blind phase search with an optional 4th-power frequency offset estimation ahead of
+ * it (optic/dsp/carrierRecovery.py:37-169 cpr, 172-223 bps, 333-371 fourthPowerFOE; optic/dsp/carrierRecoveryGPU.py bpsGPU).
+ *   x           (n, nModes) row-major, complex128 (SSF_M_C128) or complex64 (SSF_M_C64), host or device; never written
+ *   const_tab   M (re, im) pairs: the constellation the distances are taken to, as cpr normalises it (single precision, widened)
+ *   sig_out     (n, nModes) complex128, host or device: pnorm(x e^{j phase}), the norm over all modes together
+ *   phase_out   (n, nModes) float64, host or device, may be NULL (ssf_cpr): np.unwrap(4 phi, axis=0) / 4 of the raw test phases
+ *   fo_out      nModes frequency offsets [Hz], host; may be NULL (ssf_cpr); written only with runFOE
+ * For every mode, symbol k and test phase phi_b = b (pi/2) / B the search takes min_m |x_k e^{j phi_b} - c_m|^2, sums it over
+ * symbols k - Nh .. k + Nh (symbols outside [0, n) enter as zeros, as the reference pads) and picks the first minimum over b.
+ * The minimum distances stay in LDS; sums run in a fixed order, so results repeat bit for bit and do not depend on the tiling.
+ * Limits: 2 <= M <= 1024, 1 <= B <= 1024, 0 <= Nh <= 1023, n >= 2, 1 <= nModes <= 64, 1 <= P <= 1024.  Arithmetic is double
+ * whatever the input type (the reference rounds a complex64 signal back to single after the frequency offset compensation). */
+typedef struct {
+    int64_t n;                    /* symbols per mode */
+    int32_t nModes, M;
+    int32_t dtype;                /* SSF_M_C128 or SSF_M_C64 */
+    int32_t B;                    /* test phases */
+    int32_t Nh;                   /* half window: cpr passes N / 2 */
+    int32_t runFOE;               /* 1: ssf_foe with (Fs, P) and the joint norm ahead of the search */
+    int32_t P;                    /* power of the offset estimator: 4, or M for 'psk' */
+    int32_t reserved;
+    double  Fs;                   /* symbol rate 1 / Ts [Hz] */
+} ssf_cpr_params;
+int  ssf_cpr(int device, const ssf_cpr_params *params, const double *const_tab, const void *x, void *sig_out, double *phase_out,
+             double *fo_out);
+/* the raw test phase of every symbol: phase_out (n, nModes) float64, host or device */
+int  ssf_bps(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t Nh, int32_t B, int32_t M, const double *const_tab,
+             const void *x, double *phase_out);
+/* fourthPowerFOE: per mode fo = f[argmax |fft(x ** P)|] / P with f = fftshift(Fs fftfreq(n)), the first maximum in that order;
+ * sig_out = x exp(-j 2 pi fo k / Fs), (n, nModes) complex128, host or device; fo_out: nModes, host */
+int  ssf_foe(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t P, double Fs, const void *x, void *sig_out,
+             double *fo_out);
+
 #ifdef __cplusplus
 }
 #endif

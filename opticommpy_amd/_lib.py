@@ -81,6 +81,12 @@ class MetricsResult(C.Structure):
                 ("MI", C.c_double), ("EVM", C.c_double), ("bit_errors", C.c_int64), ("symbol_errors", C.c_int64), ("n", C.c_int64)]
 
 
+class CprParams(C.Structure):
+    """ssf_cpr_params (include/ssf.h)."""
+    _fields_ = [("n", C.c_int64), ("nModes", C.c_int32), ("M", C.c_int32), ("dtype", C.c_int32), ("B", C.c_int32), ("Nh", C.c_int32),
+                ("runFOE", C.c_int32), ("P", C.c_int32), ("reserved", C.c_int32), ("Fs", C.c_double)]
+
+
 METRICS_DTYPES = {"complex128": 0, "complex64": 1, "float64": 2, "float32": 3}              # ssf_metrics_dtype
 METRICS_BER, METRICS_GMI, METRICS_MI, METRICS_EVM, METRICS_EVM_BLIND = 1, 2, 4, 8, 16       # ssf_metrics_want
 
@@ -148,6 +154,12 @@ SYMBOLS = {
     "ssf_pnorm": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "ssf_signal_power": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     "ssf_demodulate": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "ssf_cpr": (C.c_int, [C.c_int, C.POINTER(CprParams), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.POINTER(C.c_double)]),
+    "ssf_bps": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p,
+                          C.c_void_p]),
+    "ssf_foe": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
+                          C.POINTER(C.c_double)]),
     "ssf_device_copy_bandwidth": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_linear_channel": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p]),

@@ -725,4 +725,53 @@ int ssf_demodulate(int device, int64_t count, int32_t dtype, int32_t M, const do
     return rc ? set_err(rc, "ssf_demodulate: " + err) : SSF_OK;
 }
 
+// ---- carrier phase recovery (engine_cpr.hip): every check comes before the first allocation or launch
+static const char *cpr_bad_shape(int64_t n, int32_t nModes, int32_t dtype) {
+    if (n < 2) return "n must be at least 2";
+    if (nModes < 1 || nModes > 64) return "nModes must be 1 .. 64";
+    if (dtype != SSF_M_C128 && dtype != SSF_M_C64) return "dtype must be complex128 or complex64";
+    return nullptr;
+}
+static const char *cpr_bad_search(int32_t Nh, int32_t B, int32_t M) {
+    if (M < 2 || M > 1024) return "M must be 2 .. 1024";
+    if (B < 1 || B > 1024) return "B must be 1 .. 1024";
+    if (Nh < 0 || Nh > 1023) return "the half window must be 0 .. 1023";
+    return nullptr;
+}
+static bool cpr_bad_foe(int32_t P, double Fs) { return P < 1 || P > 1024 || !(Fs > 0) || !std::isfinite(Fs); }
+
+int ssf_cpr(int device, const ssf_cpr_params *p, const double *const_tab, const void *x, void *sig_out, double *phase_out,
+            double *fo_out) {
+    if (!p || !const_tab || !x || !sig_out) return set_err(SSF_ERR_BAD_ARG, "ssf_cpr: NULL argument");
+    if (const char *m = cpr_bad_shape(p->n, p->nModes, p->dtype)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_cpr: ") + m);
+    if (const char *m = cpr_bad_search(p->Nh, p->B, p->M)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_cpr: ") + m);
+    if (p->runFOE && cpr_bad_foe(p->P, p->Fs)) return set_err(SSF_ERR_BAD_ARG, "ssf_cpr: P must be 1 .. 1024 and Fs positive");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::cpr_run(device, p, const_tab, x, sig_out, phase_out, fo_out, &err);
+    return rc ? set_err(rc, "ssf_cpr: " + err) : SSF_OK;
+}
+
+int ssf_bps(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t Nh, int32_t B, int32_t M, const double *const_tab,
+            const void *x, double *phase_out) {
+    if (!const_tab || !x || !phase_out) return set_err(SSF_ERR_BAD_ARG, "ssf_bps: NULL argument");
+    if (const char *m = cpr_bad_shape(n, nModes, dtype)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_bps: ") + m);
+    if (const char *m = cpr_bad_search(Nh, B, M)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_bps: ") + m);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::cpr_bps(device, n, nModes, dtype, Nh, B, M, const_tab, x, phase_out, &err);
+    return rc ? set_err(rc, "ssf_bps: " + err) : SSF_OK;
+}
+
+int ssf_foe(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t P, double Fs, const void *x, void *sig_out,
+            double *fo_out) {
+    if (!x || !sig_out || !fo_out) return set_err(SSF_ERR_BAD_ARG, "ssf_foe: NULL argument");
+    if (const char *m = cpr_bad_shape(n, nModes, dtype)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_foe: ") + m);
+    if (cpr_bad_foe(P, Fs)) return set_err(SSF_ERR_BAD_ARG, "ssf_foe: P must be 1 .. 1024 and Fs positive");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::cpr_foe(device, n, nModes, dtype, P, Fs, x, sig_out, fo_out, &err);
+    return rc ? set_err(rc, "ssf_foe: " + err) : SSF_OK;
+}
+
 }  // extern "C"

@@ -153,6 +153,13 @@ int metrics_pnorm(int device, int64_t count, int dtype, const void *x, void *y, 
 int metrics_power(int device, int64_t count, int64_t rows, int dtype, const void *x, double *out, std::string *err);
 int metrics_demod(int device, int64_t count, int dtype, int M, const double *const_raw, const void *symb, int32_t *bits_out,
                   std::string *err);
+// engine_cpr.hip (arguments already checked by ssf_api.hip)
+int cpr_run(int device, const ssf_cpr_params *p, const double *table, const void *x, void *sig_out, double *phase_out, double *fo_out,
+            std::string *err);
+int cpr_bps(int device, int64_t n, int nModes, int dtype, int Nh, int B, int M, const double *table, const void *x, double *phase_out,
+            std::string *err);
+int cpr_foe(int device, int64_t n, int nModes, int dtype, int P, double Fs, const void *x, void *sig_out, double *fo_out,
+            std::string *err);
 
 inline int fail(ssf_plan *p, int code, const std::string &msg) {
     if (p) p->err = msg;
