@@ -9,8 +9,8 @@ import numpy as np
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "metrics")
 CASES = sorted(os.path.basename(p)[len("metrics_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "metrics_*.npz")))
-EXPECTED_CASES = ["pam4_12dB", "psk8_12dB", "qam16_12dB", "qam16_4modes", "qam16_clip", "qam16_transposed", "qam256_24dB_1d",
-                  "qam64_18dB", "qam64_c64", "qam64_shaped", "qpsk_8dB"]
+EXPECTED_CASES = ["bpsk_6dB", "pam128", "pam4_12dB", "psk32", "psk8_12dB", "qam1024_1d", "qam16_12dB", "qam16_4modes", "qam16_clip",
+                  "qam16_transposed", "qam256_24dB_1d", "qam64_18dB", "qam64_c64", "qam64_shaped", "qpsk_8dB"]
 REL = 1e-9          # SNR [dB], GMI, NGMI, MI, EVM against the reference: the project's bound for double-precision receiver functions
 EXACT = ("BER", "SER")
 CLOSE = ("SNR", "GMI", "NGMI", "MI", "EVM")
