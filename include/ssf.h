@@ -565,6 +565,51 @@ int  ssf_bps(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t Nh, i
 int  ssf_foe(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t P, double Fs, const void *x, void *sig_out,
              double *fo_out);
 
+/* ---- adaptive MIMO equalizer on the device (optic/dsp/equalization.py:125-351 mimoAdaptEqualizer, 354-516 coreAdaptEq and the
+ * update rules nlmsUp, cmaUp, rdeUp, dardeUp, ddlmsUp), the stage between decimate / edc and cpr.
+ *   x           (n, nModes) row-major, complex128 (SSF_M_C128) or complex64 (SSF_M_C64), host or device; never written.  The
+ *               nTaps / 2 zeros the reference pads at both ends are not stored: the kernels supply them
+ *   ref         (nref, nModes) of ref_dtype, host or device; NULL unless a stage is SSF_EQ_NLMS or SSF_EQ_DARDE; never written
+ *   stages      nStages records, host: the stages are contiguous in one symbol index, stage 0 is repeated numIter times over
+ *               its symbols (carrying H), symbols beyond the sum of the stage lengths stay zero
+ *   const_tab   M (re, im) pairs, host: the decision constellation of SSF_EQ_DDLMS
+ *   radii_tab   nRadii ascending radii, host: the decision radii of SSF_EQ_RDE
+ *   H_inout     (nModes^2, nTaps) complex128, host or device, row k + N nModes filters input mode N into output mode k: the
+ *               initial coefficients in, the final ones out
+ *   sig_out     (total, nModes) complex128, host or device;  errsq_out (nModes, total) float64, host or device, may be NULL:
+ *               |e|^2 of every symbol, 0 for a static stage and beyond the last stage
+ * Symbol i reads the padded samples i SpS .. i SpS + nTaps - 1;  total = (n + 2 (nTaps / 2) - nTaps) / SpS + 1.
+ * With y_k the output of mode k, x_N the window of input mode N and e the error:
+ *   NLMS    e = ref_k - y_k,                        H += mu e conj(x_N) / ||x_N||^2
+ *   DDLMS   e = c[argmin |y_k - c|] - y_k,          H += mu e conj(x_N)              (the first minimum)
+ *   CMA     e = Rcma - |y_k|^2,                     H += mu e y_k conj(x_N)
+ *   RDE     e = R[argmin |R - |y_k||]^2 - |y_k|^2,  the same update;   DARDE  e = |ref_k|^2 - |y_k|^2, the same update
+ *   STATIC  outputs with H as the stage before left it, no update.
+ * Row k + N nModes of H is driven by y_k alone: one wavefront per output mode walks the symbols with its nModes nTaps
+ * coefficients in registers, no wave waits for another, sums run in a fixed order and results repeat bit for bit.
+ * Limits: 1 <= nModes <= 4, 1 <= nTaps <= 64, 1 <= SpS <= 8, n >= nTaps, 2 <= M <= 1024, 1 <= nRadii <= 1024.  Arithmetic is
+ * double whatever the input types. */
+typedef enum { SSF_EQ_NLMS = 0, SSF_EQ_CMA = 1, SSF_EQ_RDE = 2, SSF_EQ_DARDE = 3, SSF_EQ_DDLMS = 4, SSF_EQ_STATIC = 5 } ssf_eq_alg;
+typedef struct {
+    int64_t L;                    /* output symbols of the stage, >= 1 */
+    int32_t alg;                  /* ssf_eq_alg */
+    int32_t reserved;
+    double  mu;                   /* step size (the reference rounds it to single precision first) */
+} ssf_eq_stage;
+typedef struct {
+    int64_t n;                    /* input samples per mode */
+    int64_t total;                /* output symbols per mode (totalNumSymb) */
+    int64_t nref;                 /* rows of ref */
+    int32_t nModes, nTaps, SpS;
+    int32_t dtype, ref_dtype;     /* SSF_M_C128 or SSF_M_C64 */
+    int32_t nStages, numIter;
+    int32_t M, nRadii;
+    int32_t reserved;
+    double  Rcma;                 /* mean |c|^4 / mean |c|^2 */
+} ssf_eq_params;
+int  ssf_mimo_eq(int device, const ssf_eq_params *params, const ssf_eq_stage *stages, const double *const_tab, const double *radii_tab,
+                 void *H_inout, const void *x, const void *ref, void *sig_out, double *errsq_out);
+
 #ifdef __cplusplus
 }
 #endif

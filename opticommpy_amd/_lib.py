@@ -87,6 +87,28 @@ class CprParams(C.Structure):
                 ("runFOE", C.c_int32), ("P", C.c_int32), ("reserved", C.c_int32), ("Fs", C.c_double)]
 
 
+class EqStage(C.Structure):
+    """ssf_eq_stage (include/ssf.h)."""
+    _fields_ = [("L", C.c_int64), ("alg", C.c_int32), ("reserved", C.c_int32), ("mu", C.c_double)]
+
+
+class EqParams(C.Structure):
+    """ssf_eq_params (include/ssf.h)."""
+    _fields_ = [("n", C.c_int64), ("total", C.c_int64), ("nref", C.c_int64), ("nModes", C.c_int32), ("nTaps", C.c_int32),
+                ("SpS", C.c_int32), ("dtype", C.c_int32), ("ref_dtype", C.c_int32), ("nStages", C.c_int32), ("numIter", C.c_int32),
+                ("M", C.c_int32), ("nRadii", C.c_int32), ("reserved", C.c_int32), ("Rcma", C.c_double)]
+
+
+EQ_ALGS = {"nlms": 0, "cma": 1, "rde": 2, "da-rde": 3, "dd-lms": 4, "static": 5}             # ssf_eq_alg
+EQ_CHUNK = 64              # output symbols the serial equalizer kernel stages per chunk (eq_kernels.h: kChunk)
+EQ_STAGE_ELEMS = 1024      # ... unless ((c - 1) SpS + nTaps) nModes input values would exceed its staging buffer (kStageElems)
+
+
+def eq_chunk(nModes, nTaps, SpS):
+    """Output symbols per staging chunk of the serial equalizer kernel for a geometry (eq_kernels.h: chunk_symbols)."""
+    return min(EQ_CHUNK, (EQ_STAGE_ELEMS // nModes - nTaps) // SpS + 1)
+
+
 METRICS_DTYPES = {"complex128": 0, "complex64": 1, "float64": 2, "float32": 3}              # ssf_metrics_dtype
 METRICS_BER, METRICS_GMI, METRICS_MI, METRICS_EVM, METRICS_EVM_BLIND = 1, 2, 4, 8, 16       # ssf_metrics_want
 
@@ -160,6 +182,8 @@ SYMBOLS = {
                           C.c_void_p]),
     "ssf_foe": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                           C.POINTER(C.c_double)]),
+    "ssf_mimo_eq": (C.c_int, [C.c_int, C.POINTER(EqParams), C.POINTER(EqStage), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssf_device_copy_bandwidth": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_linear_channel": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p]),

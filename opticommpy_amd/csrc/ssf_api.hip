@@ -774,4 +774,42 @@ int ssf_foe(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t P, dou
     return rc ? set_err(rc, "ssf_foe: " + err) : SSF_OK;
 }
 
+// ---- adaptive MIMO equalizer (engine_eq.hip): every check comes before the first allocation or launch
+static const char *eq_bad(const ssf_eq_params *p, const ssf_eq_stage *st, const void *ref) {
+    if (p->nModes < 1 || p->nModes > 4) return "nModes must be 1 .. 4";
+    if (p->nTaps < 1 || p->nTaps > 64) return "nTaps must be 1 .. 64";
+    if (p->SpS < 1 || p->SpS > 8) return "SpS must be 1 .. 8";
+    if (p->n < p->nTaps) return "n must be at least nTaps";
+    if (p->dtype != SSF_M_C128 && p->dtype != SSF_M_C64) return "dtype must be complex128 or complex64";
+    if (p->total != (p->n + 2 * (p->nTaps / 2) - p->nTaps) / p->SpS + 1) return "total must be (n + 2 (nTaps / 2) - nTaps) / SpS + 1";
+    if (p->M < 2 || p->M > 1024) return "M must be 2 .. 1024";
+    if (p->nRadii < 1 || p->nRadii > 1024) return "nRadii must be 1 .. 1024";
+    if (p->numIter < 1) return "numIter must be at least 1";
+    if (p->nStages < 1) return "nStages must be at least 1";
+    if (!std::isfinite(p->Rcma)) return "Rcma must be finite";
+    int64_t sum = 0;
+    bool aided = false;
+    for (int s = 0; s < p->nStages; ++s) {
+        if (st[s].alg < SSF_EQ_NLMS || st[s].alg > SSF_EQ_STATIC) return "unknown algorithm";
+        if (st[s].L < 1 || st[s].L > p->total - sum) return "every stage needs L >= 1 and their sum at most total";
+        if (!std::isfinite(st[s].mu)) return "mu must be finite";
+        sum += st[s].L;
+        aided = aided || st[s].alg == SSF_EQ_NLMS || st[s].alg == SSF_EQ_DARDE;
+    }
+    if (aided && !ref) return "a data-aided stage needs ref";
+    if (ref && p->ref_dtype != SSF_M_C128 && p->ref_dtype != SSF_M_C64) return "ref_dtype must be complex128 or complex64";
+    if (ref && p->nref < (aided ? sum : 1)) return "ref must have at least as many rows as the stages have symbols";
+    return nullptr;
+}
+
+int ssf_mimo_eq(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const double *const_tab, const double *radii_tab,
+                void *H_inout, const void *x, const void *ref, void *sig_out, double *errsq_out) {
+    if (!p || !stages || !const_tab || !radii_tab || !H_inout || !x || !sig_out) return set_err(SSF_ERR_BAD_ARG, "ssf_mimo_eq: NULL argument");
+    if (const char *m = eq_bad(p, stages, ref)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_mimo_eq: ") + m);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::eq_run(device, p, stages, const_tab, radii_tab, H_inout, x, ref, sig_out, errsq_out, &err);
+    return rc ? set_err(rc, "ssf_mimo_eq: " + err) : SSF_OK;
+}
+
 }  // extern "C"

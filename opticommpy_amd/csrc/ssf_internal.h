@@ -160,6 +160,9 @@ int cpr_bps(int device, int64_t n, int nModes, int dtype, int Nh, int B, int M, 
             std::string *err);
 int cpr_foe(int device, int64_t n, int nModes, int dtype, int P, double Fs, const void *x, void *sig_out, double *fo_out,
             std::string *err);
+// engine_eq.hip (arguments already checked by ssf_api.hip)
+int eq_run(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const double *table, const double *radii, void *H_inout,
+           const void *x, const void *ref, void *sig_out, double *errsq_out, std::string *err);
 
 inline int fail(ssf_plan *p, int code, const std::string &msg) {
     if (p) p->err = msg;
