@@ -522,6 +522,8 @@ struct HipBackend {
         const int cols = (block / a.npol) / ((1 << a.log2N1) / (a.vpt == 8 ? 8 : 16));
         return !a.N2 && a.vpt != 8 && pick_col_sg<T>(a.log2N1, cols, SG_FIN) != nullptr;
     }
+    // the row kernels that carry the second round of a paired launch (fused_kernels.h: pair_row_length; pick_row)
+    bool can_pair_rows(int l2, int block) const { return l2 >= 10 && l2 <= 12 && block == 256; }
     // raise the dynamic-LDS cap of a kernel the first time THIS backend (= this plan, hence this
     // device) launches it; the attribute is per device, so the record must not be shared
     std::vector<const void *> armed;

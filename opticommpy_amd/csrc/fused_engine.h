@@ -37,6 +37,15 @@ static inline const char *tune_env(const char *name) {
 #endif
 }
 
+// Can the backend's row kernel for rows of 2^l2 run the second round of a paired launch (fused_kernels.h: pair_row_length)?  A
+// backend that does not say (the emulator, which steps the one run-time-length body) can at every length.
+template <class B, class = void> struct PairRows {
+    static bool ok(const B &, int, int) { return true; }
+};
+template <class B> struct PairRows<B, std::void_t<decltype(&B::can_pair_rows)>> {
+    static bool ok(const B &b, int l2, int block) { return b.can_pair_rows(l2, block); }
+};
+
 struct Split {
     int l1, l2;   // log2 N1 (column length), log2 N2 (row length)
 };
@@ -238,6 +247,10 @@ template <typename T, class Backend> class FusedCore {
     // (run_span; fused_kernels.h: stage_group): +1.5 ... 2.3 % steps/s at config 2, 3 of 3 (profiles/r5_ab_col_split.txt).2 = a
     // transforming kernel (H, ADV, rare) and an observing one (FIN).  SSF_COL_SPLIT in experiment builds.
     int col_split = 1;           // (experiment builds: SSF_COL_SPLIT=0 -- the general kernel at every launch)
+    // Paired row stage (fused_kernels.h, the note at Ctrl::last_nit): in a fixed-step run the row launch in front of a final stage also runs the
+    // next step's first half step, and the host leaves that step's own row launch out.  On where the field fills the chip (and the
+    // stage-specialised pattern is enqueued); SSF_ROW_PAIR=0|1 in experiment builds forces it off, or on at under-filled sizes.
+    int row_pair = -1;           // -1: by size
     bool split_ok = true;        // ... until rare stages turn out to be the rule in this call (then the general kernel for the rest of it
     int split_penalty = 0;       //     and for the next kSplitPenalty calls of the plan)
     static constexpr int kSplitPenalty = 8;
@@ -314,6 +327,7 @@ template <typename T, class Backend> class FusedCore {
     int init() {
         if (const char *e = tune_env("SSF_LIM0_BOUND")) lim0_bound = std::atoi(e) != 0;
         if (const char *e = tune_env("SSF_COL_SPLIT")) col_split = std::atoi(e);
+        if (const char *e = tune_env("SSF_ROW_PAIR")) row_pair = std::atoi(e) != 0;
         // Fields that do not fill the chip -- fewer than two 16-value waves per SIMD: rows x N <= 2^20 values per unit, i.e. up to
         // 2^19 samples for a complex128 pair, 2^20 for a packed complex64 pair -- run on the 8-value kernels (twice the waves
         // and workgroups, shorter dependent chains per thread) with one row per workgroup: measured +7 ... +75 % there
@@ -506,6 +520,8 @@ template <typename T, class Backend> class FusedCore {
         a.vpt = row_v;
         a.prio = lanes_hint <= 1 ? 1 : 0;
         a.tw_off = N2mix ? 0 : row_tw_off;
+        a.T0 = T0;
+        a.T1 = T1;
         return a;
     }
     ColArgs<T> col_args(int npol, int mode) const {
@@ -721,9 +737,10 @@ template <typename T, class Backend> class FusedCore {
         k.tr_lim = tr_lim;
         return k;
     }
-    void launch_mk_row(const MkConst &k) {
+    void launch_mk_row(const MkConst &k, bool pair = false) {
         RowArgs<T> a = row_args();
         a.use_ctrl = 1;
+        a.pair = pair ? 1 : 0;
         a.cin = ctrl + (size_t)(seq & 1) * units;
         a.cout = ctrl + (size_t)((seq + 1) & 1) * units;
         a.k = k;
@@ -864,6 +881,16 @@ template <typename T, class Backend> class FusedCore {
                                be.can_split_cols(col_args(kPacked ? 1 : 2, CM_MK), col_block_mk);
         bool general_chunk = false;
         int stalls = 0, pos = 0;                 // pos: position in the predicted pattern (kept from chunk to chunk)
+        // Paired row stages (the note at Ctrl::last_nit) ride in the pattern only: one unit (RowArgs::T0 / T1 are not moved per unit), double
+        // precision, radix-2^n 16-value rows on a kernel that carries the second round, fixed step.
+        // The device pairs wherever it can (every step that a step of the same size follows in the span), and the host leaves out the row launch in front of H
+        // after every step it expects to have been paired -- it follows z with the device's own arithmetic (pick_hz).  A wrong guess
+        // in either direction costs idle launches only: a row launch that finds ST_NEED_H does nothing, and an H launch that finds
+        // ST_AFTER_S leaves the state to the next row launch, after which the pattern meets the state again at the next H slot.
+        const bool can_pair = can_split && units == 1 && std::is_same<T, double>::value && !N1mix && !N2mix && row_v == 16 && !p.nlprMethod &&
+                              PairRows<Backend>::ok(be, sp.l2, row_block) && (row_pair < 0 ? !underfilled : row_pair != 0);
+        bool skip_row = false;                   // the step the pattern has just finished was paired: its successor has its row stage
+        double z_sim = 0.0;                      // where the step at the pattern's position starts
         long long idle_pairs = 0;                // pairs enqueued since a step last finished
         for (;;) {
             // [Row, Col] pairs still needed for this span: (1 + nIter) per step.  A surplus pair is a no-op launch
@@ -886,11 +913,19 @@ template <typename T, class Backend> class FusedCore {
             int chunk = (int)std::min(512.0, std::max(2.0, std::ceil(est)));
             if (can_split && split_ok && general_chunk) chunk = std::min(chunk, 8);
             else if (use_split && sr.n_it == 0) chunk = std::min(chunk, 4 * (n_pred + 1));     // nothing known yet: a short look first
+            const bool pairing = use_split && can_pair;
+            z_sim = cs[0].z;
+            skip_row = pairing && pos == 0 && cs[0].state == ST_NEED_H;
             for (int i = 0; i < chunk; ++i) {
-                launch_mk_row(k);
+                if (!(pairing && pos == 0 && skip_row)) launch_mk_row(k, pairing);
                 int sg = SG_ALL;
                 if (use_split) {
                     sg = pos == 0 ? (SG_H | SG_RARE) : pos < n_pred ? SG_ADV : SG_FIN;
+                    if (pairing && pos >= n_pred) {                                   // the step ends here: was its last row stage paired?
+                        const double hz_sim = pick_hz(k, z_sim, 0.0);
+                        skip_row = z_sim + hz_sim < k.Lspan && pick_hz(k, z_sim + hz_sim, 0.0) == hz_sim;
+                        z_sim += hz_sim;
+                    }
                     pos = pos >= n_pred ? 0 : pos + 1;
                 }
                 launch_mk_col(k, CM_MK, sg);

@@ -49,8 +49,10 @@ enum {
     ST_AFTER_S = 1,    // Row: new step: step size / operator, first half linear step             -> NEED_H
     ST_NEED_H = 2,     // Col: E_hd out, first rotation, forward column FFT                       -> ROW_ITER
     ST_ROW_ITER = 3,   // Row: evaluate pending convergence sums, second linear step of iterate it -> NEED_I
+                       //      (paired, see Ctrl::last_nit: + the first half step of the next step in the same launch)
     ST_NEED_I = 4,     // Col: E_fd(it).  Not final: next iterate + sums of lim_{it+1}            -> ROW_ITER
                        //      final: field out, next step's Pch + forward FFT         -> AFTER_S | SPAN_DONE
+                       //      (after a paired row stage: -> NEED_H, the next step's first half step is in G already)
     ST_SPAN_DONE = 6,
     ST_REDO0 = 7,      // Col: rebuild iterate 0 as the final one (lim_0 < tol)                   -> ROW_ITER
     // The final stage of a step that another step follows stores the field at ONE sample in sixteen -- all that the next step's
@@ -70,7 +72,7 @@ struct LinOp {          // exp(argLimOp * hz/2) / N evaluated from the bin index
 
 struct Ctrl {           // device-resident step state, double-buffered by launch parity
     int state, it, cur, hz_valid;
-    int final_;         // the I stage of iterate `it` is the last one of this step
+    int final_;         // the I stage of iterate `it` is the last one of this step (2: ... after a paired row stage, see below)
     int pend0, pendn;   // partial sums of lim_0 / lim_it are waiting for the next Row launch
     int cap0;           // iterate 0 ended the step only because maxIter == 1 (lim_0 decides non-convergence)
     int pcur, redo_;    // current Pch buffer; iterate 0 is being rebuilt as final
@@ -81,6 +83,15 @@ struct Ctrl {           // device-resident step state, double-buffered by launch
     int gscale;         // G holds the column spectrum of the field DIVIDED by N1: the final I stage of the last step did not
                         // rewrite it (see mk_col_stage); the next row stage multiplies its operator by N1
     int last_nit;       // iterations of the latest finished step (the host predicts the stage sequence from it: FusedCore::run_span)
+    // Paired row stage (fixed step, RowArgs::pair).  The row launch in front of the final stage and the ST_AFTER_S row launch of the
+    // next step are the same sandwich on the same values: the second one's forward transform undoes the inverse transform the first
+    // one has just done.  A row launch that knows its iterate is the final one and that another step of the same size follows in
+    // the span therefore runs both from its registers: G -> forward, x lin(hz/2), inverse -> G1 (the step-end spectrum the final
+    // stage observes), then forward, x the next step's operator (x N1), inverse -> G.  G1 goes to T[1 - cur], which is dead from the start of a step to
+    // its final stage, and that stage reads it there tile by tile before it writes the field into the same tile.  (The step in
+    // front of the short last step of a span is not paired: its second sandwich would need a new operator, i.e. a third inlined
+    // copy of make_linop -- 6 KB more row kernel next to a 64 KB instruction cache, and spilled registers -- for one launch per span.)
+    // That row launch leaves final_ = kFinalPaired for the final stage, which then goes on to ST_NEED_H.
     long long pend0_idx;// trace row lim_0 belongs to
     double z, hz;
     long long steps, iterations, nonconv, trace_n;
@@ -88,6 +99,8 @@ struct Ctrl {           // device-resident step state, double-buffered by launch
     long long n_recovered;          // step-start fields recovered (ST_RECOVER_A)
     LinOp lin;
 };
+
+constexpr int kFinalPaired = 2;
 
 struct MkConst {        // per-execute constants (by value)
     double Lspan, hz_fixed, tol, maxRot, c8g, sgn, lin_a, lin_b, w2, invN;
@@ -484,6 +497,9 @@ template <typename T> struct RowArgs {
     int prio;                 // 1: issue priority by phase (s_setprio); 0 when several plans share the GPU (lanes)
     int tw_off;               // single precision: byte offset of the workgroup's twiddle table in LDS (kTwLdsBytes behind the transform area)
     int N1mix;                // > 0: the column length when it is not 1 << log2N1 (col_mixed_body: N = N1mix x N2, both 2^a 3^b 5^c)
+    int pair;                 // Manakov, fixed step: the row stage in front of a final stage may run the next step's first half step too
+    cx<T> *T0, *T1;           // (the note at Ctrl::last_nit) -- the time-domain fields: T[1 - cur] receives the step-end spectrum G1
+                              // (one unit only: unit_view does not move them, and batches of units are not paired)
 };
 // number of rows (column length) of the N1 x N2 matrix a row stage works on
 template <typename T> SSF_HD long long row_n1(const RowArgs<T> &a) { return a.N1mix ? (long long)a.N1mix : 1ll << a.log2N1; }
@@ -580,12 +596,31 @@ SSF_HD void ctrl_forward(const Ctrl *cin, Ctrl *cout, int nwords) {
 #endif
 }
 
+// a value that is the same in every lane, as a scalar (device code)
+SSF_HD int uniform_i(int x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_readfirstlane(x);
+#else
+    return x;
+#endif
+}
+SSF_HD double uniform_d(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
+#else
+    return x;
+#endif
+}
+struct RowPair {        // what a paired row launch needs for its second sandwich (the note at Ctrl::last_nit)
+    bool on = false;
+    int cur = 0;         // which of T0 / T1 holds the field at the step start
+};
 // Control-block handling of a Manakov Row launch: evaluates the convergence sums the last column stage left
 // (part: this thread's first two entries of each, fetched by the caller before its row), decides final / redo,
 // derives a new step size and operator when needed, and lets the lead thread write the next control block.
 // Returns false if this launch has nothing to transform; lo receives the operator.  Uses the first 4 KiB of LDS.
 template <typename T, class Ctx>
-SSF_HD bool row_ctrl(Ctx &ctx, const RowArgs<T> &a, const double (&part)[2][4], LinOp &lo) {
+SSF_HD bool row_ctrl(Ctx &ctx, const RowArgs<T> &a, const double (&part)[2][4], LinOp &lo, RowPair *rp = nullptr) {
     LinOp *lsh = (LinOp *)ctx.lds;
     // Only the fields used here are read (scalar loads); the lead thread forwards the block
     // word by word and patches what changed.  A private copy of the whole struct makes the
@@ -598,7 +633,9 @@ SSF_HD bool row_ctrl(Ctx &ctx, const RowArgs<T> &a, const double (&part)[2][4], 
     int n_state = c_state, n_final = c.final_, n_cap0 = c_cap0, n_hzv = c.hz_valid;
     int add_nonconv = 0, add_ahead = 0;
     const long long c_nonconv = c.nonconv, c_ahead = c.n_ahead;      // (read before the block is forwarded: see mk_col_stage)
-    double n_hz = c.hz;
+    const int c_cur = c.cur;
+    const double c_z = c.z, c_hz = c.hz;
+    double n_hz = c_hz;
     double *red = (double *)(ctx.lds) + 64;
     const bool lead = ctx.bid == 0 && ctx.tid == 0;
     bool act = c_state == ST_AFTER_S || c_state == ST_ROW_ITER || c_state == ST_RECOVER_ROW;
@@ -673,11 +710,22 @@ SSF_HD bool row_ctrl(Ctx &ctx, const RowArgs<T> &a, const double (&part)[2][4], 
     }
     if (act && c_state == ST_AFTER_S && c_gscale) lo.mag *= (double)row_n1(a);           // (G = spectrum / N1: mk_col_stage)
     if (act) n_state = c_state == ST_AFTER_S ? ST_NEED_H : c_state == ST_RECOVER_ROW ? ST_RECOVER_B : ST_NEED_I;
+    // the final iterate of a fixed step that another step of the same size follows (the final stage's own test of `more`, and the
+    // step size it will hand on): both sandwiches
+    bool pair = false;
+    if (rp) {
+        pair = a.pair && act && !new_lin && c_state == ST_ROW_ITER && n_final && !a.k.adaptive && c_z + c_hz < a.k.Lspan &&
+               pick_hz(a.k, c_z + c_hz, 0.0) == c_hz;
+        // (the decision is the same in every thread of the launch, the compiler cannot know: as a scalar it keeps the second round's
+        //  control flow, step size and destination out of the vector registers, which the transforms need to the last one)
+        rp->on = uniform_i(pair ? 1 : 0) != 0;
+        rp->cur = c_cur;
+    }
     if (lead) {
         ctrl_forward(a.cin, a.cout, (int)((new_lin ? offsetof(Ctrl, lin) : sizeof(Ctrl)) / 8));
         Ctrl *n = a.cout;
         n->state = n_state;
-        n->final_ = n_final;
+        n->final_ = pair ? kFinalPaired : n_final;
         n->pend0 = 0;
         n->pendn = 0;
         n->cap0 = n_cap0;
@@ -811,9 +859,9 @@ template <typename T> constexpr bool wt_rows() {
     return sizeof(scalar_t<T>) == 8 ? (SSF_WT_ROWS & 1) != 0 : sizeof(T) == 8 ? (SSF_WT_ROWS & 2) != 0 : (SSF_WT_ROWS & 4) != 0;
 }
 template <int V, typename T, class Ctx>
-SSF_HD void row_store(Ctx &ctx, const RowArgs<T> &a, const PassPlan &p, int f, int b, const cx<T> *v) {
+SSF_HD void row_store(Ctx &ctx, const RowArgs<T> &a, cx<T> *G, const PassPlan &p, int f, int b, const cx<T> *v) {
     const int fpw = ctx.nthreads / p.tpf;
-    cx<T> *base = a.G + (((long long)ctx.bid * fpw) << a.log2N2);       // first row of this workgroup (wave-uniform)
+    cx<T> *base = G + (((long long)ctx.bid * fpw) << a.log2N2);         // first row of this workgroup (wave-uniform)
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (wt_rows<T>()) {
         const unsigned bytes = (unsigned)(((size_t)fpw << a.log2N2) * sizeof(cx<T>));
@@ -842,6 +890,42 @@ SSF_HD void row_store(Ctx &ctx, const RowArgs<T> &a, const PassPlan &p, int f, i
     for (int q = 0; q < V; ++q) g[b + p.tpf * q] = v[q];
 }
 
+// a value the optimiser cannot see through (device code; the emulator has no register file to protect)
+SSF_HD int opaque_i(int x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
+}
+// The operator is the same in every lane, but it reaches the row stage through control flow the compiler must take for divergent
+// (and from LDS when it is new), i.e. in 40 vector registers that stay occupied through the whole forward transform.  As scalars
+// they leave the vector registers to the transform: what lets the two-round kernels stay inside 256 registers without spilling.
+SSF_HD void uniform_linop(LinOp &l) {
+    l.cth = uniform_d(l.cth);
+    l.mag = uniform_d(l.mag);
+#pragma unroll
+    for (int m = 0; m < 9; ++m) {
+        l.Cre[m] = uniform_d(l.Cre[m]);
+        l.Cim[m] = uniform_d(l.Cim[m]);
+    }
+}
+SSF_HD double opaque_d(double x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(x));
+#endif
+    return x;
+}
+// Row kernels that carry the second round of a paired launch: on the device the ones with a compile-time length of 2^10 ... 2^12,
+// two workgroups of 256 threads per CU with 256 registers each, where the loop costs three registers and no scratch memory (the
+// run-time-length kernel spills as it is, the longer rows run at 128 registers); the emulator steps the run-time-length body.
+constexpr bool pair_row_length(int LG) {
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
+    return LG >= 10 && LG <= 12;
+#else
+    (void)LG;
+    return true;
+#endif
+}
 // LG > 0: row length fixed at compile time (index math folds to immediates); 0: runtime
 // V = values per thread: 16 (256 registers, two waves per SIMD) or 8 (128 registers, four waves per SIMD: while the waves
 // of one workgroup wait for their row or for their stores to drain, the other workgroup of the CU has the SIMDs)
@@ -903,15 +987,18 @@ template <typename T, int LG, int V = 16, class Ctx> SSF_HD void row_body(Ctx &c
 #endif
     // single precision: the next-to-last pass takes its hi + lo factors from a table in LDS, built while the row is in flight (TwSrc)
     constexpr bool kTab = (SSF_TW_TAB & 1) && sizeof(scalar_t<T>) == 4;
-    TwSrc<T> tws;
+    tw_entry_t<T> *tab = nullptr;
     if (kTab) {
-        tw_entry_t<T> *tab = (tw_entry_t<T> *)(ctx.lds + a.tw_off);
+        tab = (tw_entry_t<T> *)(ctx.lds + a.tw_off);
         tw_lds_build<T>(ctx, p, tab);
-        tws.lds = tab;
     }
+    // the paired row stage (the note at Ctrl::last_nit) exists in the 16-value double-precision kernels only
+    // (not with SSF_SPEC_G, whose column stages fetch G before they know where their spectrum is)
+    constexpr bool kPair = !SSF_SPEC_G && V == 16 && sizeof(T) == 8 && sizeof(scalar_t<T>) == 8 && pair_row_length(LG);
+    RowPair rp;
     if (a.use_ctrl) {
         ctx.issue_fence();
-        if (!row_ctrl(ctx, a, part, lo)) return;
+        if (!row_ctrl(ctx, a, part, lo, kPair ? &rp : nullptr)) return;
     } else if (a.lin) {
         lo = *a.lin;
     }
@@ -926,59 +1013,117 @@ template <typename T, int LG, int V = 16, class Ctx> SSF_HD void row_body(Ctx &c
     // With the forward transform above the inverse one (rows) and inverse > time domain > forward (columns) the late
     // workgroup catches up while the early one is in a later phase: +3 % steps/s at config 2 (profiles/r3_ab_runs.txt);
     // off (a.prio = 0) when several plans share the GPU, where it costs 4 % (profiles/r3_lanes_prio_wt.txt).
-    if (a.prio) ctx.template setprio<2>();
     const int last = p.npass - 1;
-#if SSF_EARLY_BASES
-    // Everything that depends on the thread's position only -- the twiddle bases of all passes (one sincospi each; the inverse
-    // transform conjugates them) and the two sines / cosines of the linear operator -- is evaluated HERE, while the row is still
-    // in flight and the VALU has nothing else to do (appendix #44).
-    Lin16Bases lb{};
-    const bool lin16 = (a.use_ctrl || a.lin) && p.lg(last) == lgV;
-    {
+    // One sandwich per round.  A paired launch goes round twice: the second round starts from the values the first one has just
+    // stored, and both rounds are the same code, so each gives what an unpaired launch of these kernels gives.
+    cx<T> *gdst = kPair && rp.on ? (rp.cur ? a.T0 : a.T1) : a.G;
+    // The kernels that can go round twice make everything that takes a sine and a cosine in front of the loop: the twiddle bases of
+    // the passes (the forward transform conjugates them as the inverse one always did) and the two phasors of a thread's bins in
+    // the operator, which both rounds share but for its magnitude (same step size: row_ctrl).  Inside the loop the compiler hoists
+    // the constants of those evaluations out of it and, out of registers there, parks them in scratch memory; the loop now holds
+    // power trees, products and butterflies only, and gets the bases as opaque values so that the trees are not hoisted either.
+    TwSrc<T> twp;
+    Lin16Bases lbp{};
+    if constexpr (kPair) {
 #pragma unroll
         for (int i = 0; i < kTwMaxPass; ++i) {
-            if (i < p.npass && p.lgLn(i) > 0 && !(kTab && i == p.npass - 2)) {
-                tws.base[i] = tw_base(+1, pass_j(p, i, b), pass_lgLi(p, i));
-                tws.have[i] = true;
+            if (SSF_TW_REUSE && i < p.npass && p.lgLn(i) > 0) {
+                twp.base[i] = tw_base(+1, pass_j(p, i, b), pass_lgLi(p, i));
+                twp.have[i] = true;
             }
         }
-        if (lin16) lb = lin16_bases<V>(cth_pre, k1 + ((long long)rev_pos(p, reg_pos(p, last, b, 0)) << a.log2N1), log2N);
-        ctx.issue_fence();
+        // (the fixed-kernel convolution has no operator: no phasors are made for it.  The operator's move to scalar registers stays
+        //  outside the branch, on zeros there -- forty register moves; inside it the kernel spills two registers)
+        const bool has_op = a.use_ctrl || a.lin;
+        if (!has_op) lo = LinOp{};
+        uniform_linop(lo);
+        if (has_op && p.lg(last) == lgV) lbp = lin16_bases<V>(lo.cth, k1 + ((long long)rev_pos(p, reg_pos(p, last, b, 0)) << a.log2N1), log2N);
     }
-#endif
-    fft_dif<-1, V, kTab>(ctx, p, b, v, l, tws);
-    ctx.mark(2);
-    if (a.prio) ctx.template setprio<1>();
-    // registers now hold pass-(p-1) positions; bin k = k1 + N1 * rev(pos)
-    if (!a.use_ctrl && !a.lin) {                 // fixed-kernel convolution: multiplier array in this kernel's spectrum order
-        if (a.fwd_only) {
+#pragma clang loop unroll(disable)
+    for (int round = 0;; ++round) {
+        // (the thread's position is made opaque per round in the kernels that can go round twice: everything that depends on it alone --
+        //  the twiddle power trees, the store offsets -- would otherwise be hoisted out of the loop and kept in registers across both
+        //  rounds, a hundred spilled registers per lane; the other instantiations compile as before)
+        const int br = kPair ? opaque_i(b) : b, fr = kPair ? opaque_i(f) : f, k1r = kPair ? opaque_i(k1) : k1;
+        TwSrc<T> tws;
+        if (kTab) tws.lds = tab;
+        Lin16Bases lbr{};
+        if constexpr (kPair) {
 #pragma unroll
-            for (int idx = 0; idx < V; ++idx) g[reg_pos(p, last, b, idx)] = v[idx];
-            return;
+            for (int i = 0; i < kTwMaxPass; ++i) {
+                tws.have[i] = twp.have[i];
+                if (twp.have[i]) tws.base[i] = mk<double>(opaque_d(twp.base[i].re), opaque_d(twp.base[i].im));
+            }
+            lbr.A = mk<double>(opaque_d(lbp.A.re), opaque_d(lbp.A.im));
+            lbr.B1 = mk<double>(opaque_d(lbp.B1.re), opaque_d(lbp.B1.im));
+            lbr.cth = lbp.cth;
         }
-        const cx<T> *h = a.harr + ((size_t)k1 << a.log2N2);
-#pragma unroll
-        for (int idx = 0; idx < V; ++idx) v[idx] = v[idx] * h[reg_pos(p, last, b, idx)];
-    } else if (p.lg(last) == lgV) {
+        if (a.prio) ctx.template setprio<2>();
 #if SSF_EARLY_BASES
-        if (lo.cth != lb.cth) lb = lin16_bases<V>(lo.cth, k1 + ((long long)rev_pos(p, reg_pos(p, last, b, 0)) << a.log2N1), log2N);
-        apply_lin16<V>(lo, lb, v);
-#else
-        const long long k0 = k1 + ((long long)rev_pos(p, reg_pos(p, last, b, 0)) << a.log2N1);
-        apply_lin16<V>(lo, k0, log2N, v);
-#endif
-    } else {
+        // Everything that depends on the thread's position only -- the twiddle bases of all passes (one sincospi each; the inverse
+        // transform conjugates them) and the two sines / cosines of the linear operator -- is evaluated HERE, while the row is still
+        // in flight and the VALU has nothing else to do (appendix #44).
+        Lin16Bases lb{};
+        const bool lin16 = (a.use_ctrl || a.lin) && p.lg(last) == lgV;
+        {
 #pragma unroll
-        for (int idx = 0; idx < V; ++idx) {
-            const long long k = k1 + ((long long)rev_pos(p, reg_pos(p, last, b, idx)) << a.log2N1);
-            v[idx] = mul_by_d(v[idx], lin_at(lo, k, log2N));
+            for (int i = 0; i < kTwMaxPass; ++i) {
+                if (i < p.npass && p.lgLn(i) > 0 && !(kTab && i == p.npass - 2)) {
+                    tws.base[i] = tw_base(+1, pass_j(p, i, br), pass_lgLi(p, i));
+                    tws.have[i] = true;
+                }
+            }
+            if (lin16) lb = lin16_bases<V>(cth_pre, k1r + ((long long)rev_pos(p, reg_pos(p, last, br, 0)) << a.log2N1), log2N);
+            ctx.issue_fence();
+        }
+#endif
+        fft_dif<-1, V, kTab>(ctx, p, br, v, l, tws);
+        ctx.mark(2);
+        if (a.prio) ctx.template setprio<1>();
+        // registers now hold pass-(p-1) positions; bin k = k1 + N1 * rev(pos)
+        if (!a.use_ctrl && !a.lin) {                 // fixed-kernel convolution: multiplier array in this kernel's spectrum order
+            if (a.fwd_only) {
+#pragma unroll
+                for (int idx = 0; idx < V; ++idx) g[reg_pos(p, last, br, idx)] = v[idx];
+                return;
+            }
+            const cx<T> *h = a.harr + ((size_t)k1r << a.log2N2);
+#pragma unroll
+            for (int idx = 0; idx < V; ++idx) v[idx] = v[idx] * h[reg_pos(p, last, br, idx)];
+        } else if (p.lg(last) == lgV) {
+#if SSF_EARLY_BASES
+            if (lo.cth != lb.cth) lb = lin16_bases<V>(lo.cth, k1r + ((long long)rev_pos(p, reg_pos(p, last, br, 0)) << a.log2N1), log2N);
+            apply_lin16<V>(lo, lb, v);
+#else
+            if constexpr (kPair) apply_lin16<V>(lo, lbr, v);
+            else {
+                const long long k0 = k1r + ((long long)rev_pos(p, reg_pos(p, last, br, 0)) << a.log2N1);
+                apply_lin16<V>(lo, k0, log2N, v);
+            }
+#endif
+        } else {
+#pragma unroll
+            for (int idx = 0; idx < V; ++idx) {
+                const long long k = k1r + ((long long)rev_pos(p, reg_pos(p, last, br, idx)) << a.log2N1);
+                v[idx] = mul_by_d(v[idx], lin_at(lo, k, log2N));
+            }
+        }
+        ctx.mark(3);
+        fft_dit<+1, V, kTab>(ctx, p, br, v, l, tws);
+        if (a.prio) ctx.template setprio<0>();
+        ctx.mark(4);
+        row_store<V>(ctx, a, gdst, p, fr, br, v);
+        if constexpr (!kPair) break;
+        else {
+            if (round || !rp.on) break;
+            // the next step's operator as its ST_AFTER_S row stage would find it: the same step size (row_ctrl), so the same operator,
+            // and G holds the spectrum / N1 as far as that stage is concerned (Ctrl::gscale)
+            lo = a.cin->lin;
+            lo.mag *= (double)row_n1(a);
+            uniform_linop(lo);
+            gdst = a.G;
         }
     }
-    ctx.mark(3);
-    fft_dit<+1, V, kTab>(ctx, p, b, v, l, tws);
-    if (a.prio) ctx.template setprio<0>();
-    ctx.mark(4);
-    row_store<V>(ctx, a, p, f, b, v);
     ctx.mark(5);
     ctx.flush(0);
 }
@@ -1411,6 +1556,7 @@ SSF_HD void mk_advance(Ctx &ctx, const G &g, const ColArgs<T> &a, cx<T> *v, cons
 struct MkColStage {
     bool do_inv = false, do_fwd = false, final_ = false, more = false, exact0 = true;
     bool sparse = false;      // final stage: store the field at the samples the next step's bound of lim_0 reads only
+    bool paired = false;      // final stage: the spectrum to observe is in T[1 - cur], G belongs to the next step already (the note at Ctrl::last_nit)
     int op = -1;
     struct { int state, it, cur, pcur; double z, hz; } c{};
 };
@@ -1440,6 +1586,7 @@ template <class Ctx, class Args> SSF_HD void mk_col_stage(Ctx &ctx, const Args &
     // after the block's stores they are vector loads the compiler must wait for one by one (cin and cout may alias for all it
     // knows) -- up to five more memory round trips in front of the lead workgroup's own work
     const int c_exact0 = a.cin->exact0, c_redo = a.cin->redo_;
+    const bool c_paired = a.cin->final_ == kFinalPaired;
     const long long c_trace_n = a.cin->trace_n, c_steps = a.cin->steps, c_iters = a.cin->iterations;
     const long long c_rebuilt = a.cin->n_rebuilt, c_recovered = a.cin->n_recovered;
     if (c.state == ST_NEED_S) {
@@ -1462,6 +1609,7 @@ template <class Ctx, class Args> SSF_HD void mk_col_stage(Ctx &ctx, const Args &
         // a fixed-step run is about to take its short last step (whose lim_0 is rounding-sized).
         st.sparse = final_ && more && !a.k.exact_lim0 && !a.cin->dense &&
                     (a.k.adaptive || pick_hz(a.k, c.z + c.hz, 0.0) == c.hz);
+        st.paired = more && c_paired;
     } else if (c.state == ST_REDO0) {
         op = 3;
         do_fwd = true;
@@ -1488,7 +1636,9 @@ template <class Ctx, class Args> SSF_HD void mk_col_stage(Ctx &ctx, const Args &
             n->state = ST_ROW_ITER;
             n->it = 0;
             n->final_ = a.k.maxIter == 1;
-            n->pend0 = n->pendn = 0;
+            // (pend0 stays: it is clear after a row stage, and after a paired step's final stage -- no row stage in between -- the
+            //  sums of lim_0 that stage may have left wait for the row stage that follows this launch)
+            n->pendn = 0;
         } else if (op == 4) {
             n->state = ST_RECOVER_ROW;
         } else if (op == 3 || op == 5) {
@@ -1535,8 +1685,9 @@ template <class Ctx, class Args> SSF_HD void mk_col_stage(Ctx &ctx, const Args &
             n->t_sparse = st.sparse ? 1 : 0;
             n->dense = 0;
             if (more) {
-                n->gscale = 1;
-                n->state = ST_AFTER_S;
+                // (paired: the row stage in front of this launch was the next step's ST_AFTER_S stage too)
+                n->gscale = st.paired ? 0 : 1;
+                n->state = st.paired ? ST_NEED_H : ST_AFTER_S;
                 n->pcur = c.pcur ^ 1;
                 if (a.k.adaptive) n->hz_valid = 0;
                 else {
@@ -1564,7 +1715,7 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
     // ---- what does this launch do? ------------------------------------------------------
     bool do_inv = false, do_fwd = false;
     int op = -1;     // Manakov: 0 = S (span start), 1 = H, 2 = I, 3 = rebuild iterate 0
-    bool final_ = false, more = false, exact0 = true, sparse = false;
+    bool final_ = false, more = false, exact0 = true, sparse = false, paired = false;
     struct { int state, it, cur, pcur; double z, hz; } c{};
     double *red = (double *)ctx.lds;
     ctx.mark(0);
@@ -1592,6 +1743,7 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
         more = st.more;
         exact0 = st.exact0;
         sparse = st.sparse;
+        paired = kgFIN && st.paired;
         op = st.op;
         c.state = st.c.state;
         c.it = st.c.it;
@@ -1626,13 +1778,21 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
     cx<T> e_pre{};
     if (do_inv) {
         if (!(kMk && SSF_SPEC_G)) {
+            auto load_spectrum = [&](const cx<T> *Gin) {
 #pragma unroll
-            for (int q = 0; q < V; ++q) {
-                v[q] = g.ld(a.G, g.rowbase + g.freq_off(q));
+                for (int q = 0; q < V; ++q) {
+                    v[q] = g.ld(Gin, g.rowbase + g.freq_off(q));
 #if SSF_LOAD_ORDER
-                if ((q & 3) == 3) ctx.issue_fence();         // (appendix #43: the inter-pass twiddles are applied in this order, group by group)
+                    if ((q & 3) == 3) ctx.issue_fence();     // (appendix #43: the inter-pass twiddles are applied in this order, group by group)
 #endif
-            }
+                }
+            };
+            // (after a paired row stage the final stage finds its spectrum in the buffer it is about to fill: same tile, loaded first.
+            //  In place only because every thread's loads are consumed before the first exchange barrier of the inverse transform and
+            //  the stores come behind it: the transform needs two passes or more -- columns of 32 up with 16 values per thread -- or one
+            //  thread per column, which holds for every column length that can pair.  The emulator's workgroups cannot show a violation.)
+            if constexpr (kMk && kgFIN) load_spectrum(paired ? Tnew : a.G);
+            else load_spectrum(a.G);
         }
         // the one sample per thread that the bound of lim_0 compares with the field at the step start: fetched here, behind the
         // spectrum, instead of where it is used -- there the load was issued and waited for on the spot (s_waitcnt vmcnt(0) right
