@@ -610,6 +610,67 @@ typedef struct {
 int  ssf_mimo_eq(int device, const ssf_eq_params *params, const ssf_eq_stage *stages, const double *const_tab, const double *radii_tab,
                  void *H_inout, const void *x, const void *ref, void *sig_out, double *errsq_out);
 
+/* ---- soft-decision FEC on the device: the soft demapper and the LDPC belief-propagation decoder that end the reference's chain
+ * (optic/comm/metrics.py:198-239 calcLLR; optic/comm/fec.py:347-758 sumProductAlgorithm, minSumAlgorithm, decodeLDPC).
+ *
+ * ssf_calc_llr: llr_out[i b + j] = log p0 - log p1 of bit j of symbol i, b = log2 M, with p0 / p1 the sums over the constellation
+ * points m (ascending) whose bit j is 0 / 1 of exp(-|x_i - c_m|^2 / sigma2) px_m.  Arithmetic is double; an underflowed sum gives
+ * +-inf as in the reference.
+ *   x           n values of `dtype` (SSF_M_C128 or SSF_M_C64), host or device; never written
+ *   const_tab   M (re, im) pairs, host;  px: M priors, host;  bitmap: (M, b) row-major int32 of 0 / 1, host
+ *   llr_out     n b float64, host or device
+ * M is a power of two, 2 .. 1024; sigma2 > 0. */
+int  ssf_calc_llr(int device, int64_t n, int32_t dtype, int32_t M, double sigma2, const double *const_tab, const int32_t *bitmap,
+                  const double *px, const void *x, double *llr_out);
+
+/* The Tanner graph of a parity-check matrix H (m x n, E ones), uploaded once and used by any number of decodes.  The four arrays are
+ * those fec.py:388-411 builds, all int32, host:
+ *   check_offsets   m + 1: the edges of check c are check_offsets[c] .. check_offsets[c + 1] - 1 (edge id = position in H's CSR)
+ *   edge_var        E: the variable of every edge (H's CSR column indices, ascending inside a check)
+ *   var_offsets     n + 1;  var_edge_indices  E: the edge ids of variable v, ascending check index
+ * Checked here, before anything is uploaded: offsets start at 0, rise and end at E; every index in range; every check has
+ * 1 .. 64 edges and every variable at most 64; var_edge_indices lists, for every variable, exactly its own edges. */
+typedef struct ssf_ldpc_graph ssf_ldpc_graph;
+int  ssf_ldpc_graph_create(int device, int32_t m, int32_t n, int32_t E, const int32_t *check_offsets, const int32_t *edge_var,
+                           const int32_t *var_offsets, const int32_t *var_edge_indices, ssf_ldpc_graph **out);
+int  ssf_ldpc_graph_destroy(ssf_ldpc_graph *graph);
+
+/* ssf_ldpc_decode: flooding belief propagation, SPA or MSA, of numCodewords codewords at once.
+ *   llr_in      (n_, numCodewords) row-major -- or (numCodewords, n_) with transposed = 1 -- of in_dtype, host or device; never
+ *               written.  Clipped to +-200 on load; with n_ < n the variables n_ .. n - 1 are punctured (LLR 0) and not returned
+ *   llr_out     the posterior LLRs in the same orientation, of `prec`;  bits_out int8 in the same orientation: llr_out < 0
+ *   fail_out    numCodewords int8: 0 where the hard decisions satisfied every check at some iteration, else 1
+ *   iter_out    numCodewords uint32, may be NULL: the index of that iteration, or maxIter - 1
+ *   all four host or device
+ * Per codeword: V->C messages start at the LLR; an iteration is check update, variable update, posterior and parity test; the
+ * codeword stops at the first iteration that satisfies every check and keeps that iteration's posterior.  A variable sums
+ * llr + its C->V messages in ascending check index and sends that sum minus the edge's own message.  MSA: first minimum, second
+ * minimum and the product of signs (val >= 0 -> +1).  SPA: tanh(x / 2) once per edge, leave-one-out products from prefix and
+ * suffix products, clip to +-0.999999, 2 atanh.
+ * Engines: SSF_FEC_LDS runs one workgroup per codeword through all iterations in one launch with messages, LLRs, posteriors and
+ * decisions in LDS (graphs with ((E + E / 32 + 1) + 2 n) sizeof(prec) + n + 32 bytes <= 160 KiB); SSF_FEC_GLOBAL keeps them in device
+ * memory and launches twice per iteration over all codewords, skipping converged ones by a device-side flag; SSF_FEC_AUTO takes
+ * the first when the graph fits.  Both run the same node bodies in the same edge order: results are identical between them and
+ * repeat bit for bit.  sync_every > 0 (global engine): the host reads the flags every sync_every iterations and stops when every
+ * codeword has converged; 0 never reads them. */
+enum ssf_fec_alg { SSF_FEC_SPA = 0, SSF_FEC_MSA = 1 };
+enum ssf_fec_prec { SSF_FEC_F64 = 0, SSF_FEC_F32 = 1 };
+enum ssf_fec_engine { SSF_FEC_AUTO = 0, SSF_FEC_LDS = 1, SSF_FEC_GLOBAL = 2 };
+typedef struct {
+    int32_t n_;                   /* rows of llr_in per codeword, 1 .. n */
+    int32_t numCodewords;
+    int32_t maxIter;              /* >= 1 */
+    int32_t alg;                  /* ssf_fec_alg */
+    int32_t prec;                 /* ssf_fec_prec: message and output precision */
+    int32_t in_dtype;             /* ssf_fec_prec: type of llr_in */
+    int32_t transposed;
+    int32_t engine;               /* ssf_fec_engine */
+    int32_t sync_every;
+    int32_t reserved;
+} ssf_ldpc_params;
+int  ssf_ldpc_decode(int device, const ssf_ldpc_graph *graph, const ssf_ldpc_params *params, const void *llr_in, void *llr_out,
+                     int8_t *bits_out, int8_t *fail_out, uint32_t *iter_out);
+
 #ifdef __cplusplus
 }
 #endif

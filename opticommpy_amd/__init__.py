@@ -26,9 +26,10 @@ from .metrics import calcEVM, demodulateGray, fastBERcalc, monteCarloGMI, monteC
 from . import cpr  # noqa: F401  (a callable module: oa.cpr(sigIn, param) is the reference's cpr)
 from .cpr import bps, bpsGPU, fourthPowerFOE  # noqa: F401
 from .equalization import mimoAdaptEqualizer  # noqa: F401
+from .fec import calcLLR, decodeLDPC, readAlist  # noqa: F401
 
 __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMapping", "DeviceArray", "to_device", "firFilter", "lowPassFIR", "decimate", "delaySignal", "iqMixing", "pbs", "photodiode", "balancedPD",
            "opticalHybrid2x4", "coherentReceiver", "pdmCoherentReceiver", "pdmCoherentReceiverChain", "parameters", "ssfm", "manakovSSF", "manakovDBP", "nlinPhaseRot", "convergenceCondition", "edfa", "edc", "blockwiseFFTConv", "linearFiberChannel",
            "setPowerforParSSFM", "checkGPU", "last_run", "set_device", "set_engine",
            "metrics", "fastBERcalc", "monteCarloGMI", "monteCarloMI", "calcEVM", "demodulateGray", "pnorm", "signalPower",
-           "cpr", "bps", "bpsGPU", "fourthPowerFOE", "mimoAdaptEqualizer"]
+           "cpr", "bps", "bpsGPU", "fourthPowerFOE", "mimoAdaptEqualizer", "calcLLR", "decodeLDPC", "readAlist"]

@@ -99,6 +99,26 @@ class EqParams(C.Structure):
                 ("M", C.c_int32), ("nRadii", C.c_int32), ("reserved", C.c_int32), ("Rcma", C.c_double)]
 
 
+class LdpcParams(C.Structure):
+    """ssf_ldpc_params (include/ssf.h)."""
+    _fields_ = [("n_", C.c_int32), ("numCodewords", C.c_int32), ("maxIter", C.c_int32), ("alg", C.c_int32), ("prec", C.c_int32),
+                ("in_dtype", C.c_int32), ("transposed", C.c_int32), ("engine", C.c_int32), ("sync_every", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+FEC_ALGS = {"SPA": 0, "MSA": 1}                                                             # ssf_fec_alg
+FEC_PRECS = {"float64": 0, "float32": 1}                                                    # ssf_fec_prec
+FEC_ENGINES = {"auto": 0, "lds": 1, "global": 2}                                            # ssf_fec_engine
+FEC_MAX_DEGREE = 64        # largest check or variable degree (fec_kernels.h: kMaxDeg)
+FEC_LDS_BUDGET = 160 * 1024    # bytes of LDS the one-workgroup decoder may use (fec_kernels.h: kLdsBudget)
+
+
+def fec_lds_bytes(E, n, prec):
+    """LDS the one-workgroup LDPC decoder needs for a graph of E edges and n variables (fec_kernels.h: lds_bytes)."""
+    w = 8 if FEC_PRECS[prec] == 0 else 4
+    return ((E + (E >> 5) + 1) + 2 * n) * w + 16 + ((n + 15) // 16) * 16
+
+
 EQ_ALGS = {"nlms": 0, "cma": 1, "rde": 2, "da-rde": 3, "dd-lms": 4, "static": 5}             # ssf_eq_alg
 EQ_CHUNK = 64              # output symbols the serial equalizer kernel stages per chunk (eq_kernels.h: kChunk)
 EQ_STAGE_ELEMS = 1024      # ... unless ((c - 1) SpS + nTaps) nModes input values would exceed its staging buffer (kStageElems)
@@ -184,6 +204,13 @@ SYMBOLS = {
                           C.POINTER(C.c_double)]),
     "ssf_mimo_eq": (C.c_int, [C.c_int, C.POINTER(EqParams), C.POINTER(EqStage), C.POINTER(C.c_double), C.POINTER(C.c_double),
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_calc_llr": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                               C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "ssf_ldpc_graph_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_void_p)]),
+    "ssf_ldpc_graph_destroy": (C.c_int, [C.c_void_p]),
+    "ssf_ldpc_decode": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(LdpcParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]),
     "ssf_device_copy_bandwidth": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_linear_channel": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p]),

@@ -812,4 +812,93 @@ int ssf_mimo_eq(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, 
     return rc ? set_err(rc, "ssf_mimo_eq: " + err) : SSF_OK;
 }
 
+// ---- soft-decision FEC (engine_fec.hip): every check comes before the first allocation, upload or launch
+int ssf_calc_llr(int device, int64_t n, int32_t dtype, int32_t M, double sigma2, const double *const_tab, const int32_t *bitmap,
+                 const double *px, const void *x, double *llr_out) {
+    if (!const_tab || !bitmap || !px || (n > 0 && (!x || !llr_out))) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_llr: NULL argument");
+    if (n < 0) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_llr: n must not be negative");
+    if (dtype != SSF_M_C128 && dtype != SSF_M_C64) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_llr: dtype must be complex128 or complex64");
+    if (M < 2 || M > 1024 || (M & (M - 1))) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_llr: M must be a power of two, 2 .. 1024");
+    if (!(sigma2 > 0) || !std::isfinite(sigma2)) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_llr: sigma2 must be positive");
+    int b = 0;
+    while ((1 << b) < M) ++b;
+    for (int i = 0; i < M * b; ++i)
+        if (bitmap[i] != 0 && bitmap[i] != 1) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_llr: bitmap must hold 0 and 1 only");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::fec_calc_llr(device, n, dtype, M, sigma2, const_tab, bitmap, px, x, llr_out, &err);
+    return rc ? set_err(rc, "ssf_calc_llr: " + err) : SSF_OK;
+}
+
+// the kernels index with these arrays unchecked: nothing that could send them out of bounds, or two threads to one edge, gets in
+static const char *ldpc_graph_bad(int m, int n, int E, const int32_t *co, const int32_t *ev, const int32_t *vo, const int32_t *ve,
+                                  int *max_dc) {
+    if (m < 1 || n < 1 || E < 1) return "m, n and E must be positive";
+    if (co[0] != 0 || co[m] != E) return "check_offsets must run from 0 to E";
+    if (vo[0] != 0 || vo[n] != E) return "var_offsets must run from 0 to E";
+    *max_dc = 0;
+    for (int c = 0; c < m; ++c) {
+        const int64_t d = (int64_t)co[c + 1] - co[c];
+        if (d < 1) return "every check needs at least one edge and check_offsets must rise";
+        if (d > 64) return "a check has more than 64 edges";
+        if (co[c + 1] > E) return "check_offsets must run from 0 to E";
+        if (d > *max_dc) *max_dc = (int)d;
+    }
+    for (int e = 0; e < E; ++e)
+        if (ev[e] < 0 || ev[e] >= n) return "edge_var holds an index outside 0 .. n - 1";
+    std::vector<unsigned char> seen((size_t)E, 0);
+    for (int v = 0; v < n; ++v) {
+        const int64_t d = (int64_t)vo[v + 1] - vo[v];
+        if (d < 0 || vo[v + 1] > E) return "var_offsets must rise from 0 to E";
+        if (d > 64) return "a variable has more than 64 edges";
+        for (int k = vo[v]; k < vo[v + 1]; ++k) {
+            const int e = ve[k];
+            if (e < 0 || e >= E || ev[e] != v || seen[(size_t)e]) return "var_edge_indices must list every variable's own edges once";
+            seen[(size_t)e] = 1;
+        }
+    }
+    return nullptr;
+}
+
+int ssf_ldpc_graph_create(int device, int32_t m, int32_t n, int32_t E, const int32_t *check_offsets, const int32_t *edge_var,
+                          const int32_t *var_offsets, const int32_t *var_edge_indices, ssf_ldpc_graph **out) {
+    if (!check_offsets || !edge_var || !var_offsets || !var_edge_indices || !out)
+        return set_err(SSF_ERR_BAD_ARG, "ssf_ldpc_graph_create: NULL argument");
+    *out = nullptr;
+    int max_dc = 0;
+    if (const char *msg = ldpc_graph_bad(m, n, E, check_offsets, edge_var, var_offsets, var_edge_indices, &max_dc))
+        return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ldpc_graph_create: ") + msg);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::fec_graph_create(device, m, n, E, check_offsets, edge_var, var_offsets, var_edge_indices, max_dc, out, &err);
+    return rc ? set_err(rc, "ssf_ldpc_graph_create: " + err) : SSF_OK;
+}
+
+int ssf_ldpc_graph_destroy(ssf_ldpc_graph *graph) {
+    if (!graph) return SSF_OK;
+    std::string err;
+    int rc = ssf::fec_graph_destroy(graph, &err);
+    return rc ? set_err(rc, "ssf_ldpc_graph_destroy: " + err) : SSF_OK;
+}
+
+int ssf_ldpc_decode(int device, const ssf_ldpc_graph *graph, const ssf_ldpc_params *p, const void *llr_in, void *llr_out,
+                    int8_t *bits_out, int8_t *fail_out, uint32_t *iter_out) {
+    if (!graph || !p || !llr_in || !llr_out || !bits_out || !fail_out) return set_err(SSF_ERR_BAD_ARG, "ssf_ldpc_decode: NULL argument");
+    const char *msg = nullptr;
+    if (p->n_ < 1 || p->n_ > graph->n) msg = "n_ must be 1 .. n";
+    else if (p->numCodewords < 1 || p->numCodewords > 65535) msg = "numCodewords must be 1 .. 65535";
+    else if (p->maxIter < 1 || p->maxIter > 65535) msg = "maxIter must be 1 .. 65535";
+    else if (p->alg != SSF_FEC_SPA && p->alg != SSF_FEC_MSA) msg = "alg must be SSF_FEC_SPA or SSF_FEC_MSA";
+    else if (p->prec != SSF_FEC_F64 && p->prec != SSF_FEC_F32) msg = "prec must be SSF_FEC_F64 or SSF_FEC_F32";
+    else if (p->in_dtype != SSF_FEC_F64 && p->in_dtype != SSF_FEC_F32) msg = "in_dtype must be SSF_FEC_F64 or SSF_FEC_F32";
+    else if (p->engine < SSF_FEC_AUTO || p->engine > SSF_FEC_GLOBAL) msg = "unknown engine";
+    else if (p->sync_every < 0) msg = "sync_every must not be negative";
+    else if (device != graph->device) msg = "the graph lives on another device";
+    if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ldpc_decode: ") + msg);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::fec_decode(device, graph, p, llr_in, llr_out, bits_out, fail_out, iter_out, &err);
+    return rc ? set_err(rc, "ssf_ldpc_decode: " + err) : SSF_OK;
+}
+
 }  // extern "C"

@@ -64,6 +64,12 @@ class Engine {
 
 }  // namespace ssf
 
+// the Tanner graph of ssf_ldpc_graph_create on its device: one allocation, four int32 arrays inside it
+struct ssf_ldpc_graph {
+    int device = 0, m = 0, n = 0, E = 0, max_dc = 0;
+    int *d_all = nullptr, *d_co = nullptr, *d_ev = nullptr, *d_vo = nullptr, *d_ve = nullptr;
+};
+
 struct ssf_plan {
     int device = 0;
     int64_t N = 0;
@@ -163,6 +169,14 @@ int cpr_foe(int device, int64_t n, int nModes, int dtype, int P, double Fs, cons
 // engine_eq.hip (arguments already checked by ssf_api.hip)
 int eq_run(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const double *table, const double *radii, void *H_inout,
            const void *x, const void *ref, void *sig_out, double *errsq_out, std::string *err);
+// engine_fec.hip (arguments already checked by ssf_api.hip)
+int fec_calc_llr(int device, int64_t n, int dtype, int M, double sigma2, const double *table, const int32_t *bitmap, const double *px,
+                 const void *x, double *llr_out, std::string *err);
+int fec_graph_create(int device, int m, int n, int E, const int32_t *co, const int32_t *ev, const int32_t *vo, const int32_t *ve,
+                     int max_dc, ssf_ldpc_graph **out, std::string *err);
+int fec_graph_destroy(ssf_ldpc_graph *g, std::string *err);
+int fec_decode(int device, const ssf_ldpc_graph *g, const ssf_ldpc_params *p, const void *llr_in, void *llr_out, int8_t *bits_out,
+               int8_t *fail_out, uint32_t *iter_out, std::string *err);
 
 inline int fail(ssf_plan *p, int code, const std::string &msg) {
     if (p) p->err = msg;

@@ -1,0 +1,209 @@
+"""Shared by the soft-decision FEC tests: the fixtures tests/golden/fec/*.npz (tools/gen_golden_fec.py), the bounds the test
+files hold in common, the comparison of a result against the recorded arrays and the conditions every fixture must meet.
+
+Bounds:
+  MSA               outputLLRs bit-equal to the reference's run in the same prec; decodedBits, frameErrors, lastIter equal.
+  SPA, float64      outputLLRs within 1e-9 rel-L2 per codeword and 1e-9 of the column's max |ref| per element (the project's bound
+                    for double-precision receiver functions against reference fixtures; amp <= 1e4 times library rounding of about
+                    1e-15 leaves two decades); decodedBits, frameErrors, lastIter equal.
+  SPA, float32      per codeword the distance to the reference's float64 run is at most 4 x that codeword's self_err (the
+                    reference's own float32 run against its float64 run: two independent single-precision roundings of one
+                    recursion); decisions, frameErrors, lastIter equal the reference's.
+  calcLLR           1e-9 relative per element, floored at 1e-12 absolute, where finite; equal after the clip to +-200 in the
+                    underflow case."""
+import glob
+import json
+import os
+
+import numpy as np
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "fec")
+ALIST_648 = os.path.join(GOLDEN, "LDPC_IEEE_802.11nD2_648b_R12.txt")
+CASES = sorted(os.path.basename(p)[len("ldpc_"):-len(".npz")] for p in glob.glob(os.path.join(GOLDEN, "ldpc_*.npz"))
+               if "ldpc_graph_" not in p)
+EXPECTED_CASES = ["msa_648_clip", "msa_648_iter25", "msa_648_mixed", "msa_ar4ja_punct", "spa_648_f32", "spa_648_iter25",
+                  "spa_648_mixed", "spa_648_none", "spa_ar4ja_punct"]
+LLR_CASES = ["qam16", "qam16_underflow", "qam64_shaped"]
+GRAPHS = ["648", "ar4ja"]
+PRECS = ("float64", "float32")
+REL = 1e-9                 # SPA in float64
+F32_FACTOR = 4             # SPA in float32: multiples of the reference's own single-precision distance
+LLR_REL, LLR_ABS = 1e-9, 1e-12
+AMP_MAX = 1e4
+
+
+class Param:
+    """Stand-in for the reference's parameters object: attributes only."""
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+class Csr:
+    """What a scipy.sparse.csr_matrix shows of itself to decodeLDPC."""
+
+    def __init__(self, indptr, indices, shape):
+        self.indptr, self.indices, self.shape = indptr, indices, (int(shape[0]), int(shape[1]))
+
+
+_LOADED = {}
+
+
+def load(name):
+    """A decoding fixture, read once and shared (nobody writes to it)."""
+    if name not in _LOADED:
+        z = np.load(os.path.join(GOLDEN, f"ldpc_{name}.npz"))
+        g = {k: z[k] for k in z.files}
+        g["cfg"] = json.loads(str(g["cfg"]))
+        g["n_"] = int(g["n_"])
+        for a in g.values():
+            if isinstance(a, np.ndarray):
+                a.setflags(write=False)
+        _LOADED[name] = g
+    return _LOADED[name]
+
+
+def load_llr(name):
+    z = np.load(os.path.join(GOLDEN, f"llr_{name}.npz"))
+    g = {k: z[k] for k in z.files}
+    g["cfg"] = json.loads(str(g["cfg"]))
+    g["sigma2"] = float(g["sigma2"])
+    return g
+
+
+def load_graph(key):
+    z = np.load(os.path.join(GOLDEN, f"ldpc_graph_{key}.npz"))
+    return {k: z[k] for k in z.files}
+
+
+def H_of(g):
+    return Csr(g["indptr"], g["indices"], g["shape"])
+
+
+def param(g, prec=None, **extra):
+    """The fixture's parameter object; ``prec`` is the one the case is named for unless given."""
+    cfg = g["cfg"]
+    return Param(H=H_of(g), alg=cfg["alg"], maxIter=cfg["maxIter"], prec=np.dtype(prec or cfg["prec"]).type, **extra)
+
+
+def rel_cols(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.linalg.norm(a - b, axis=0) / np.linalg.norm(b, axis=0)
+
+
+def check_conditions(g):
+    """The fixture cannot make a test pass emptily (asserted by the generator, re-checked on the stored values)."""
+    cfg = g["cfg"]
+    ncw = g["llrs"].shape[1]
+    assert ncw == 4 and g["llrs"].shape == (g["n_"], ncw) and g["llrs"].dtype == np.float64
+    assert g["out64"].dtype == np.float64 and g["out32"].dtype == np.float32 and g["out64"].shape == g["llrs"].shape
+    assert np.all(g["amp"] <= AMP_MAX) and np.all(g["amp"] > 0)
+    assert np.array_equal(g["fail32"], g["fail64"]) and np.array_equal(g["iter32"], g["iter64"]) and np.array_equal(g["bits32"], g["bits64"])
+    assert np.allclose(rel_cols(g["out32"], g["out64"]), g["self_err"], rtol=1e-6, atol=0)
+    assert np.all((g["self_err"] > 1e-8) & (g["self_err"] < 1e-3))
+    assert np.array_equal(g["bits64"], (g["out64"] < 0).astype(np.int8))
+    fail, it = g["fail64"], g["iter64"]
+    assert np.all(it[fail == 1] == cfg["maxIter"] - 1)
+    if cfg["want"] == "mixed":
+        assert 0 < fail.sum() < ncw
+    elif cfg["want"] == "none":
+        assert fail.sum() == ncw
+    elif cfg["want"] == "all_differ":
+        assert fail.sum() == 0 and len(set(it.tolist())) >= 2
+    if cfg["clip"]:
+        assert np.sum(np.abs(g["llrs"]) > 200) >= 20 and np.sum(g["llrs"] == 0) >= 20
+    if g["n_"] < cfg["n"]:
+        assert g["shape"][1] == cfg["n"] and g["n_"] == 1280
+
+
+def check_set():
+    fails = np.concatenate([load(n)["fail64"] for n in EXPECTED_CASES])
+    iters = np.concatenate([load(n)["iter64"] for n in EXPECTED_CASES])
+    assert 0 in fails and 1 in fails and len(set(iters.tolist())) >= 2
+
+
+def compare_decode(got, g, prec, label, columns=None):
+    """(decodedBits, outputLLRs, frameErrors, lastIter) of a decode with ``prec`` -- all (n_, numCodewords) -- against the fixture,
+    at the bounds of this module's docstring.  ``columns``: the fixture column every result column repeats (default: all, once)."""
+    bits, out, fail, last = (np.asarray(a) for a in got)
+    prec = np.dtype(prec).name
+    tag = "64" if prec == "float64" else "32"
+    cols = np.arange(g["llrs"].shape[1]) if columns is None else np.asarray(columns)
+    ref_same, ref64 = g["out" + tag][:, cols], g["out64"][:, cols]
+    assert out.dtype == np.dtype(prec) and bits.dtype == np.int8 and fail.dtype == np.int8 and last.dtype == np.uint32, label
+    assert out.shape == ref_same.shape and bits.shape == ref_same.shape and fail.shape == (len(cols),) and last.shape == (len(cols),), label
+    assert np.array_equal(fail, g["fail64"][cols]), (label, fail)
+    assert np.array_equal(last, g["iter64"][cols]), (label, last)
+    assert np.array_equal(bits, g["bits64"][:, cols]), label
+    assert np.array_equal(bits, (out < 0).astype(np.int8)), label
+    if g["cfg"]["alg"] == "MSA":
+        assert np.array_equal(out, ref_same), (label, float(np.max(np.abs(out - ref_same))))
+        return
+    e2 = rel_cols(out, ref64)
+    if prec == "float64":
+        emax = np.max(np.abs(out - ref64), axis=0) / np.max(np.abs(ref64), axis=0)
+        print(f"{label}: rel-L2 per codeword up to {e2.max():.2e}, element error / max |ref| up to {emax.max():.2e}")
+        assert np.all(e2 <= REL) and np.all(emax <= REL), (label, e2, emax)
+    else:
+        ratio = e2 / g["self_err"][cols]
+        print(f"{label}: distance to the float64 run / the reference's own, per codeword: {np.array2string(ratio, precision=2)}")
+        assert np.all(ratio <= F32_FACTOR), (label, ratio)
+
+
+def compare_llr(got, g, label):
+    got, want = np.asarray(got), g["llr"]
+    assert got.dtype == np.float64 and got.shape == want.shape, label
+    assert not np.any(np.isnan(got)), label
+    if g["cfg"]["name"].endswith("underflow"):
+        assert np.any(np.isinf(got)) and np.array_equal(np.isinf(got), np.isinf(want)), label
+        assert np.array_equal(np.clip(got, -200, 200)[np.isinf(want)], np.clip(want, -200, 200)[np.isinf(want)]), label
+    else:
+        assert np.all(np.isfinite(want)) and np.all(np.isfinite(got)), label
+    fin = np.isfinite(want)
+    err = np.abs(got[fin] - want[fin])
+    bound = np.maximum(LLR_REL * np.abs(want[fin]), LLR_ABS)
+    print(f"{label}: largest error / bound {float(np.max(err / bound)):.2e}")
+    assert np.all(err <= bound), (label, float(np.max(err / bound)))
+
+
+def write_emu_ldpc(path, llrs, prm, engine, transposed=False):
+    """The input file of tests/emu/emu_fec.cpp (ldpc): the arguments as the package hands them to the library.  Returns what
+    ``fec._prepare`` made of them."""
+    from opticommpy_amd import fec
+    q = fec._prepare(llrs, prm, transposed)
+    p, gr = q["params"], q["graph"]
+    with open(path, "wb") as f:
+        f.write(np.array([q["m"], q["n"], q["E"], p.n_, p.numCodewords, p.maxIter, p.alg, p.prec, p.in_dtype, p.transposed,
+                          {"lds": 1, "global": 2}[engine]], dtype=np.int64).tobytes())
+        for k in ("check_offsets", "edge_var", "var_offsets", "var_edge_indices"):
+            f.write(gr[k].astype(np.int32).tobytes())
+        f.write(np.ascontiguousarray(q["llrs"]).tobytes())
+    return q
+
+
+def read_emu_ldpc(path, q):
+    """(decodedBits, outputLLRs, frameErrors, lastIter) from the emulator's output, in the orientation of the input."""
+    p = q["params"]
+    shape, count = q["llrs"].shape, q["llrs"].size
+    raw = np.fromfile(path, dtype=np.uint8)
+    w = q["prec"].itemsize
+    out = raw[:count * w].view(q["prec"]).reshape(shape)
+    bits = raw[count * w:count * (w + 1)].view(np.int8).reshape(shape)
+    fail = raw[count * (w + 1):count * (w + 1) + p.numCodewords].view(np.int8)
+    last = raw[count * (w + 1) + p.numCodewords:].view(np.uint32)
+    assert last.shape == (p.numCodewords,)
+    return bits, out, fail, last
+
+
+def write_emu_llr(path, g):
+    from opticommpy_amd import _lib, fec
+    q = fec._prepare_llr(g["rxSymb"], g["sigma2"], g["constSymb"], g["bitMap"], g["px"])
+    with open(path, "wb") as f:
+        f.write(np.array([q["x"].shape[0], _lib.METRICS_DTYPES[q["x"].dtype.name], q["M"]], dtype=np.int64).tobytes())
+        f.write(np.array([q["sigma2"]], dtype=np.float64).tobytes())
+        f.write(q["table"].tobytes())
+        f.write(q["px"].tobytes())
+        f.write(q["bitmap"].tobytes())
+        f.write(np.ascontiguousarray(q["x"]).tobytes())
+    return q
