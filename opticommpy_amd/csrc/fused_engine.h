@@ -251,6 +251,11 @@ template <typename T, class Backend> class FusedCore {
     // next step's first half step, and the host leaves that step's own row launch out.  On where the field fills the chip (and the
     // stage-specialised pattern is enqueued); SSF_ROW_PAIR=0|1 in experiment builds forces it off, or on at under-filled sizes.
     int row_pair = -1;           // -1: by size
+    // Chained column stage (fused_kernels.h: col_body, kChain): behind a paired row launch the H kernel takes the final stage and the next
+    // step's H stage in one launch, and the host leaves out the FIN launch and that step's own H launch.  Only where the row stage
+    // pairs, and by default exactly where it pairs by default (the field fills the chip); SSF_COL_CHAIN=0|1 in experiment builds
+    // forces it off, or on wherever the row stage pairs.  Bit-equal to the unchained run.
+    int col_chain = -1;          // -1: by size
     bool split_ok = true;        // ... until rare stages turn out to be the rule in this call (then the general kernel for the rest of it
     int split_penalty = 0;       //     and for the next kSplitPenalty calls of the plan)
     static constexpr int kSplitPenalty = 8;
@@ -328,6 +333,7 @@ template <typename T, class Backend> class FusedCore {
         if (const char *e = tune_env("SSF_LIM0_BOUND")) lim0_bound = std::atoi(e) != 0;
         if (const char *e = tune_env("SSF_COL_SPLIT")) col_split = std::atoi(e);
         if (const char *e = tune_env("SSF_ROW_PAIR")) row_pair = std::atoi(e) != 0;
+        if (const char *e = tune_env("SSF_COL_CHAIN")) col_chain = std::atoi(e) != 0;
         // Fields that do not fill the chip -- fewer than two 16-value waves per SIMD: rows x N <= 2^20 values per unit, i.e. up to
         // 2^19 samples for a complex128 pair, 2^20 for a packed complex64 pair -- run on the 8-value kernels (twice the waves
         // and workgroups, shorter dependent chains per thread) with one row per workgroup: measured +7 ... +75 % there
@@ -765,9 +771,10 @@ template <typename T, class Backend> class FusedCore {
         be.launch_row(a, row_grid, row_block, row_lds, units);
         ++seq;
     }
-    void launch_mk_col(const MkConst &k, int mode, int sg = SG_ALL) {
+    void launch_mk_col(const MkConst &k, int mode, int sg = SG_ALL, bool chain = false) {
         ColArgs<T> a = col_args(kPacked ? 1 : 2, mode);
         a.sg = sg;
+        a.chain = chain ? 1 : 0;
         a.cin = ctrl + (size_t)(seq & 1) * units;
         a.cout = ctrl + (size_t)((seq + 1) & 1) * units;
         a.k = k;
@@ -889,7 +896,16 @@ template <typename T, class Backend> class FusedCore {
         // ST_AFTER_S leaves the state to the next row launch, after which the pattern meets the state again at the next H slot.
         const bool can_pair = can_split && units == 1 && std::is_same<T, double>::value && !N1mix && !N2mix && row_v == 16 && !p.nlprMethod &&
                               PairRows<Backend>::ok(be, sp.l2, row_block) && (row_pair < 0 ? !underfilled : row_pair != 0);
+        // Chained column stage: at the step-end slot of a step it expects to have been paired the host enqueues the H kernel with
+        // ColArgs::chain set instead of FIN -- it observes, and goes on with the next step's H stage -- and leaves the next step's
+        // position 0 empty (neither row nor H launch).  The empty slot still counts as a pair of the chunk, so the chunk estimate
+        // below rounds up as before: a chained step needs one launch less than its share of `est`, never more.  Wrong guesses cost
+        // idle launches only: the chaining kernel takes ANY final stage (one that was not paired: FIN alone, the next row launch
+        // and the next H-capable slot pick the state up) and, like the H kernel, the rare stages; a plain FIN kernel at a paired
+        // boundary does FIN alone and the H kernel of the next slot follows.
+        const bool can_chain = can_pair && (col_chain < 0 ? !underfilled : col_chain != 0);
         bool skip_row = false;                   // the step the pattern has just finished was paired: its successor has its row stage
+        bool skip_h = false;                     // ... and its H stage too (chained)
         double z_sim = 0.0;                      // where the step at the pattern's position starts
         long long idle_pairs = 0;                // pairs enqueued since a step last finished
         for (;;) {
@@ -915,20 +931,33 @@ template <typename T, class Backend> class FusedCore {
             else if (use_split && sr.n_it == 0) chunk = std::min(chunk, 4 * (n_pred + 1));     // nothing known yet: a short look first
             const bool pairing = use_split && can_pair;
             z_sim = cs[0].z;
+            const bool chaining = pairing && can_chain;
             skip_row = pairing && pos == 0 && cs[0].state == ST_NEED_H;
+            // (a chunk that ended on a chained launch: the step at the pattern's position has had its H stage)
+            skip_h = chaining && pos == 0 && cs[0].state == ST_ROW_ITER && cs[0].it == 0;
             for (int i = 0; i < chunk; ++i) {
+                if (chaining && pos == 0 && skip_h) {                                 // row and H stage of this step ran in the launches before
+                    skip_h = false;
+                    pos = pos >= n_pred ? 0 : pos + 1;
+                    continue;
+                }
                 if (!(pairing && pos == 0 && skip_row)) launch_mk_row(k, pairing);
                 int sg = SG_ALL;
+                bool chain = false;
                 if (use_split) {
                     sg = pos == 0 ? (SG_H | SG_RARE) : pos < n_pred ? SG_ADV : SG_FIN;
                     if (pairing && pos >= n_pred) {                                   // the step ends here: was its last row stage paired?
                         const double hz_sim = pick_hz(k, z_sim, 0.0);
                         skip_row = z_sim + hz_sim < k.Lspan && pick_hz(k, z_sim + hz_sim, 0.0) == hz_sim;
                         z_sim += hz_sim;
+                        if (chaining && skip_row) {
+                            sg = SG_H | SG_RARE;
+                            chain = skip_h = true;
+                        }
                     }
                     pos = pos >= n_pred ? 0 : pos + 1;
                 }
-                launch_mk_col(k, CM_MK, sg);
+                launch_mk_col(k, CM_MK, sg, chain);
             }
             be.d2h(cs.data(), ctrl + (size_t)(seq & 1) * units, cbytes);              // synchronising read
             if (!be.ok()) return hiperr();

@@ -1159,6 +1159,8 @@ template <typename T> struct ColArgs {
     int u_part;
     int prio;                 // see RowArgs
     int sg;                   // Manakov: stage groups the launched kernel carries (0 = SG_ALL); read by the launcher only
+    int chain;                // Manakov, the SG_H | SG_RARE kernel: also take a final stage, and behind a paired one go on with the next
+                              // step's H stage in the same launch (col_body, kChain); 0: that kernel as it was
     // column lengths with factors 3 / 5 (col_mixed_body): N = N1mix x N2, the tile (mix_cols columns x N1mix, both polarisations)
     // lives in LDS and is transformed by the mixed-radix passes of mixed_fft.h
     int N1mix, mix_cols;      // column length (0: 1 << log2N1), columns per workgroup (a power of two)
@@ -1392,14 +1394,29 @@ SSF_HD void pair_cis(Ctx &ctx, const G &g, const T *ang_own, cx<T> *rot, cx<T> *
 }
 
 // ---- Manakov time-domain building blocks (registers v = this thread's 16 samples of its row) ----
+// |v|^2 of a double-precision sample with its one fused multiply-add spelled out.  Left to the compiler, re * re + im * im
+// becomes fma(re, re, im * im) or fma(im, im, re * re) sample by sample and kernel by kernel (both products have one use, the
+// choice follows the operand order the optimiser happens to leave), and the two differ in the last place: the same final stage
+// compiled into two kernels (SG_FIN and the chaining H kernel of col_body) then writes a different Pch.  Device code only: the
+// host compiler does not contract, and the emulator keeps the plain expression.
+template <typename T> SSF_HD T norm2_pinned(cx<T> a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (std::is_same<T, double>::value) return __builtin_fma(a.im, a.im, a.re * a.re);
+    else
+#endif
+        return norm2(a);
+}
 // step start (channels.py:388-395): Pch = |Ex|^2 + |Ey|^2 -> Pbuf, block max of phi -> pmax
-template <typename T, class Ctx, class G>
-SSF_HD void mk_step_start(Ctx &ctx, const G &g, const ColArgs<T> &a, const cx<T> *v, T *Pbuf, bool lds_busy) {
+// (pw_out: the V values of Pch this thread has just formed -- both threads of a pair form every one, from the same operands in
+//  the same order, so they are the bits the x thread stores; the chained H stage of col_body takes its samples from there)
+// (MAXPHI = false: a fixed-step launch, which never reads pmax)
+template <bool MAXPHI = true, typename T, class Ctx, class G>
+SSF_HD void mk_step_start(Ctx &ctx, const G &g, const ColArgs<T> &a, const cx<T> *v, T *Pbuf, bool lds_busy, T *pw_out = nullptr) {
     constexpr int V = G::kV;
     T *shT = (T *)ctx.lds;
     T mine[V], oth[V];
 #pragma unroll
-    for (int idx = 0; idx < V; ++idx) mine[idx] = norm2(v[idx]);
+    for (int idx = 0; idx < V; ++idx) mine[idx] = norm2_pinned(v[idx]);
     if (lds_busy && !(G::kDppT && g.dpp)) ctx.sync();
     pair_swap(ctx, g, mine, oth, shT);
     const T c8g = (T)a.k.c8g;
@@ -1409,10 +1426,13 @@ SSF_HD void mk_step_start(Ctx &ctx, const G &g, const ColArgs<T> &a, const cx<T>
         const T ax = g.pol ? oth[idx] : mine[idx], ay = g.pol ? mine[idx] : oth[idx];
         const T pw = ax + ay;
         if (g.pol == 0) g.st(Pbuf, g.pbase + g.time_off(idx), pw);
-        const T phi = c8g * (pw + ax + ay) / (T)2;
-        m = (double)phi > m ? (double)phi : m;
+        if (pw_out) pw_out[idx] = pw;
+        if constexpr (MAXPHI) {
+            const T phi = c8g * (pw + ax + ay) / (T)2;
+            m = (double)phi > m ? (double)phi : m;
+        }
     }
-    if (a.k.adaptive) {
+    if (MAXPHI && a.k.adaptive) {
         m = block_max(ctx, m, (double *)ctx.lds);
         if (ctx.tid == 0) a.pmax[ctx.bid] = m;
     }
@@ -1557,6 +1577,9 @@ struct MkColStage {
     bool do_inv = false, do_fwd = false, final_ = false, more = false, exact0 = true;
     bool sparse = false;      // final stage: store the field at the samples the next step's bound of lim_0 reads only
     bool paired = false;      // final stage: the spectrum to observe is in T[1 - cur], G belongs to the next step already (the note at Ctrl::last_nit)
+    bool chain_kernel = false;  // set by the caller: the instantiation that can chain (col_body, kChain); the lead thread forwards the
+                                // control block through vector registers there
+    bool chain = false;       // set by the caller: a paired final stage goes on with the next step's H stage in this launch (col_body, kChain)
     int op = -1;
     struct { int state, it, cur, pcur; double z, hz; } c{};
 };
@@ -1625,7 +1648,9 @@ template <class Ctx, class Args> SSF_HD void mk_col_stage(Ctx &ctx, const Args &
         do_inv = do_fwd = false;
     }
     if (ctx.bid == 0 && ctx.tid == 0) {                               // forward the control block
-        ctrl_forward(a.cin, a.cout, (int)(sizeof(Ctrl) / 8));
+        // (st.chain_kernel: the block goes through vector registers -- see MkColStage)
+        const Ctrl *fsrc = st.chain_kernel ? (const Ctrl *)((const char *)a.cin + opaque_i(0)) : a.cin;
+        ctrl_forward(fsrc, a.cout, (int)(sizeof(Ctrl) / 8));
         Ctrl *n = a.cout;
         if (op == 0) {
             n->state = ST_AFTER_S;
@@ -1695,6 +1720,13 @@ template <class Ctx, class Args> SSF_HD void mk_col_stage(Ctx &ctx, const Args &
                     if (hz != c.hz) n->hz_valid = 0;
                     n->hz = hz;
                 }
+                if (st.chain && st.paired) {
+                    // chained launch: the H stage of the step that starts here runs in this launch too, so its patch (op == 1
+                    // above) goes on top of the step-end one (it = 0 already; pend0 stays, as it does there)
+                    n->state = ST_ROW_ITER;
+                    n->final_ = a.k.maxIter == 1;
+                    n->pendn = 0;
+                }
             } else n->state = ST_SPAN_DONE;
         }
     }
@@ -1712,10 +1744,24 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
     constexpr bool kMk = MODE == CM_MK;
     constexpr bool kgH = (SG & SG_H) != 0, kgADV = (SG & SG_ADV) != 0, kgFIN = (SG & SG_FIN) != 0, kgRARE = (SG & SG_RARE) != 0;
     constexpr bool kFwd = !kMk || kgH || kgADV || kgRARE;             // (the final stage never transforms forward)
+    // Chained launch (ColArgs::chain; the 16-value double-precision H + rare kernel only -- every other instantiation compiles what it
+    // did).  After a paired row stage a step's final stage and the next step's H stage are two column launches back to back on
+    // the same tile, with no row launch between them, and Pch is written by the first and read back by the second.  With a.chain
+    // set this kernel also takes a final stage (the prologue below), and where that stage was paired it goes on with the H stage
+    // in the code it runs as a launch of its own.  One launch boundary and the read of P less per paired step
+    // (FusedCore::run_span leaves out the FIN launch and the next step's row and H launches).
+    // The chained run is the unchained one bit for bit: the final stage's transform rounds here as it does in the SG_FIN kernel
+    // (see the note at its call below), and the one expression the compiler contracted differently in the two kernels, |v|^2 of
+    // Pch, has its fused multiply-add spelled out (norm2_pinned).
+    // This instantiation forwards the control block through vector registers (MkColStage::chain_kernel): fetched by scalar
+    // loads its 76 words sit in scalar registers next to the uniform values of two stages, and twelve of those were spilled
+    // into lanes of a vector register; at the top of the kernel the vector registers are free.
+    constexpr bool kChain = kMk && SG == (SG_H | SG_RARE) && V == 16 && sizeof(T) == 8 && !RAGGED && CI == 0 && !SSF_SPEC_G;
     // ---- what does this launch do? ------------------------------------------------------
     bool do_inv = false, do_fwd = false;
     int op = -1;     // Manakov: 0 = S (span start), 1 = H, 2 = I, 3 = rebuild iterate 0
     bool final_ = false, more = false, exact0 = true, sparse = false, paired = false;
+    bool st_paired = false;                                           // kChain: the final stage in front of this launch was paired
     struct { int state, it, cur, pcur; double z, hz; } c{};
     double *red = (double *)ctx.lds;
     ctx.mark(0);
@@ -1736,7 +1782,11 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
 #endif
     if (kMk) {
         MkColStage st;
-        mk_col_stage(ctx, a, st, SG);
+        if constexpr (kChain) {
+            st.chain_kernel = true;
+            st.chain = a.chain != 0 && !a.k.adaptive;                  // (the host chains fixed-step runs only)
+            mk_col_stage(ctx, a, st, st.chain ? (SG | SG_FIN) : SG);
+        } else mk_col_stage(ctx, a, st, SG);
         do_inv = st.do_inv;
         do_fwd = kFwd && st.do_fwd;
         final_ = kgFIN && (!kgADV || st.final_);
@@ -1744,6 +1794,7 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
         exact0 = st.exact0;
         sparse = st.sparse;
         paired = kgFIN && st.paired;
+        st_paired = kChain && st.paired;
         op = st.op;
         c.state = st.c.state;
         c.it = st.c.it;
@@ -1770,6 +1821,87 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
         const long long psz = g.N * a.ngroups;
         Pcur = a.P + (c.pcur ? psz : 0);
         Palt = a.P + (c.pcur ? 0 : psz);
+    }
+
+    // ---- chained launch: the final stage in front of the H stage -------------------------------
+    // The observing code of the SG_FIN kernel (the I branch below with final_ set, sixteen values, double precision): the tile of
+    // the step-end spectrum -> time samples, the sums of lim_0 when this is iterate 0, the (sparse) field store, Pch of the next
+    // step.  A final stage that was not paired ends the launch here, as a FIN launch would.  Behind a paired one the launch goes
+    // on as the H stage of the step that starts here: its roles (cur and pcur flipped; hz is the same, a paired step is followed
+    // by a step of its size), its spectrum in G, and its Pch from the registers mk_step_start leaves -- the value at
+    // own_time_off(g, j) is pw[j] in the x thread and pw[j + 8] in the y thread, the bits it would have loaded; eight values
+    // live through the inverse transform, nothing is fetched but the tile of G.
+    // Every hazard stays inside the workgroup's tile: the final stage reads its tile of T[1 - cur] and stores into it (the note at
+    // the in-place load below), the H stage reads and rewrites its tile of G, which the paired row launch finished before this
+    // launch began, and writes its tile of E_hd; the LDS scratch of mk_step_start is released by its closing barrier before the
+    // second inverse transform's first exchange.
+    T pk[kChain ? H : 1];
+    bool pk_valid = false;
+    if constexpr (kChain) {
+        if (op == 2) {                               // (an I stage passes this kernel's mask only as the final one)
+            const cx<T> *Gin = st_paired ? Tnew : a.G;
+#pragma unroll
+            for (int q = 0; q < V; ++q) {
+                v[q] = g.ld(Gin, g.rowbase + g.freq_off(q));
+#if SSF_LOAD_ORDER
+                if ((q & 3) == 3) ctx.issue_fence();
+#endif
+            }
+            cx<T> e[V];
+            if (c.it == 0 && !exact0 && lim0_bound_sample<V>(0, g.b)) e[0] = g.ld(Tcur, g.rowbase + g.time_off(0));
+            if (a.prio) ctx.template setprio<3>();
+            {
+                // (nothing kept: the H stage makes its own bases.  And the thread's position is opaque to this transform: sharing
+                //  the twiddle products with the H stage's transform changes which of them the compiler contracts into fused
+                //  multiply-adds, and with that the last bit of the factors -- each transform must round as it does in a launch
+                //  of its own, or the chained run is not the unchained one bit for bit)
+                TwSrc<T> tw1;
+                GTw gt1;
+                ColGeom<T, LG, Ctx, RAGGED, V> g1 = g;
+                g1.b = opaque_i(g.b);
+                g1.n2 = opaque_i(g.n2);
+                global_twiddle<+1, RAGGED>(g1, a.log2N1 + a.log2N2, v, gt1);
+                fft_dif<+1, V, false, kCI>(ctx, g1.p, g1.b, v, lds, tw1);
+            }
+            if (a.prio) ctx.template setprio<2>();
+            if (c.it == 0) {                         // lim_0 against the field at the step start
+                double n0 = 0, d0 = 0;
+                if (exact0) {
+#pragma unroll
+                    for (int idx = 0; idx < V; ++idx) e[idx] = g.ld(Tcur, g.rowbase + g.time_off(idx));
+                }
+#pragma unroll
+                for (int idx = 0; idx < V; ++idx) {
+                    if (exact0 || lim0_bound_sample<V>(idx, g.b)) {
+                        const double dr = (double)v[idx].re - (double)e[idx].re, di = (double)v[idx].im - (double)e[idx].im;
+                        n0 += dr * dr + di * di;
+                        d0 += (double)e[idx].re * e[idx].re + (double)e[idx].im * e[idx].im;
+                    }
+                }
+#pragma unroll
+                for (int idx = 0; idx < V; ++idx)
+                    if (!sparse || lim0_bound_sample<V>(idx, g.b)) g.st(Tnew, g.rowbase + g.time_off(idx), v[idx]);
+                block_sum2(ctx, n0, d0, red);
+                if (ctx.tid == 0) {
+                    a.pnum0[ctx.bid] = n0;
+                    a.pden0[ctx.bid] = d0;
+                }
+            } else {
+#pragma unroll
+                for (int idx = 0; idx < V; ++idx)
+                    if (!sparse || lim0_bound_sample<V>(idx, g.b)) g.st(Tnew, g.rowbase + g.time_off(idx), v[idx]);
+            }
+            if (!more) return;
+            T pw[V];
+            mk_step_start<false>(ctx, g, a, v, Palt, true, pw);     // (chained launches are fixed-step ones: mk_col_stage)
+            if (!(a.chain && st_paired)) return;
+#pragma unroll
+            for (int j = 0; j < H; ++j) pk[j] = g.pol ? pw[j + H] : pw[j];
+            pk_valid = true;
+            op = 1;
+            do_inv = do_fwd = true;
+            // (the H stage touches no buffer whose role flips but P, and its Pch is in pk)
+        }
     }
 
     // ---- inverse column transform: G -> time samples in registers -------------------------
@@ -1828,7 +1960,7 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
             T ang[H];
 #pragma unroll
             for (int j = 0; j < H; ++j) {
-                const T pw = g.ld(Pcur, g.pbase + own_time_off(g, j));
+                const T pw = kChain && pk_valid ? pk[j] : g.ld(Pcur, g.pbase + own_time_off(g, j));
                 ang[j] = shz * (c8g * (pw + pw) / (T)2);
             }
 #pragma unroll
