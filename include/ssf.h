@@ -565,6 +565,44 @@ int  ssf_bps(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t Nh, i
 int  ssf_foe(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t P, double Fs, const void *x, void *sig_out,
              double *fo_out);
 
+/* ---- sequence synchronisation on the device (optic/dsp/core.py:552-675 symbolSync, 678-698 finddelay), the stage between edc and
+ * the equalizer: the transmitted symbols aligned to the received signal.
+ *   rx          (n_rx, nModes) row-major, complex128 or complex64, host or device; never written.  With SpS > 1 it is first
+ *               decimated to one sample per symbol as ssf_decimate does (n_rx % SpS == 0)
+ *   tx          (n_tx, nModes) complex128 or complex64, host or device; never written
+ *   out         (n_tx, nModes) of tx's type, host or device: column k is tx[:, swap[k]], times rot[k], conjugated if conj[k],
+ *               rolled by -delay[k]
+ *   result      host, may be NULL: the decisions as applied
+ * SSF_SYNC_AMP correlates |tx_m| - mean with |rx_n| - mean for every pair, SSF_SYNC_REAL the complex tx_m with Re rx_n and then
+ * tx[:, swap[k]] with Im rx_k; corrMatrix[m, n] is the largest magnitude, swap its column argmax (first maximum).  Correlations
+ * are scipy's mode "full" through transforms of a power-of-two length >= n_tx + n_rx - 1; every argmax takes the lowest index.
+ * All launches of a call follow each other without a host decision; only `result` is copied back.
+ * Limits: 1 <= nModes <= 8, n_tx >= 2, n_rx / SpS >= 2, SpS >= 1, SpS * nModes <= 256. */
+enum ssf_sync_mode { SSF_SYNC_AMP = 0, SSF_SYNC_REAL = 1 };
+typedef struct {
+    int64_t n_rx;                 /* rows of rx as passed */
+    int64_t n_tx;
+    int32_t nModes, SpS;
+    int32_t mode;                 /* ssf_sync_mode */
+    int32_t rx_dtype, tx_dtype;   /* SSF_M_C128 or SSF_M_C64 */
+    int32_t reserved;
+} ssf_sync_params;
+typedef struct {
+    int64_t delay[8];
+    int32_t swap[8];
+    int32_t rot[8];               /* 0: 1, 1: -1, 2: 1j, 3: -1j */
+    int32_t conj[8];
+    double  corrMatrix[64];       /* (nModes, nModes) row-major */
+} ssf_sync_result;
+int  ssf_symbol_sync(int device, const ssf_sync_params *params, const void *rx, const void *tx, void *out, ssf_sync_result *result);
+/* finddelay: argmax |correlate(x, y)| - nx + 1 (y conjugated); x, y 1-D of any ssf_metrics_dtype, host or device; nx, ny >= 1 */
+int  ssf_finddelay(int device, int64_t nx, int64_t ny, int32_t x_dtype, int32_t y_dtype, const void *x, const void *y,
+                   int64_t *delay_out);
+/* measurement aid (tools/bench_sync.py): the transforms of one ssf_symbol_sync call alone, on the engine's own buffers and plans --
+ * nseq forward, nslots and then nslots2 inverse transforms of length L (a power of two) per round; seconds_out: device time per
+ * round over `reps` rounds after one warm-up round */
+int  ssf_sync_transform_time(int device, int64_t L, int32_t nseq, int32_t nslots, int32_t nslots2, int32_t reps, double *seconds_out);
+
 /* ---- adaptive MIMO equalizer on the device (optic/dsp/equalization.py:125-351 mimoAdaptEqualizer, 354-516 coreAdaptEq and the
  * update rules nlmsUp, cmaUp, rdeUp, dardeUp, ddlmsUp), the stage between decimate / edc and cpr.
  *   x           (n, nModes) row-major, complex128 (SSF_M_C128) or complex64 (SSF_M_C64), host or device; never written.  The

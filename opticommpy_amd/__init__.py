@@ -25,6 +25,7 @@ from . import metrics  # noqa: F401  (a callable module: oa.metrics(rx, tx, M, c
 from .metrics import calcEVM, demodulateGray, fastBERcalc, monteCarloGMI, monteCarloMI, pnorm, signalPower  # noqa: F401
 from . import cpr  # noqa: F401  (a callable module: oa.cpr(sigIn, param) is the reference's cpr)
 from .cpr import bps, bpsGPU, fourthPowerFOE  # noqa: F401
+from .sync import finddelay, symbolSync  # noqa: F401
 from .equalization import mimoAdaptEqualizer  # noqa: F401
 from .fec import calcLLR, decodeLDPC, readAlist  # noqa: F401
 
@@ -32,4 +33,4 @@ __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMa
            "opticalHybrid2x4", "coherentReceiver", "pdmCoherentReceiver", "pdmCoherentReceiverChain", "parameters", "ssfm", "manakovSSF", "manakovDBP", "nlinPhaseRot", "convergenceCondition", "edfa", "edc", "blockwiseFFTConv", "linearFiberChannel",
            "setPowerforParSSFM", "checkGPU", "last_run", "set_device", "set_engine",
            "metrics", "fastBERcalc", "monteCarloGMI", "monteCarloMI", "calcEVM", "demodulateGray", "pnorm", "signalPower",
-           "cpr", "bps", "bpsGPU", "fourthPowerFOE", "mimoAdaptEqualizer", "calcLLR", "decodeLDPC", "readAlist"]
+           "cpr", "bps", "bpsGPU", "fourthPowerFOE", "symbolSync", "finddelay", "mimoAdaptEqualizer", "calcLLR", "decodeLDPC", "readAlist"]

@@ -87,6 +87,23 @@ class CprParams(C.Structure):
                 ("runFOE", C.c_int32), ("P", C.c_int32), ("reserved", C.c_int32), ("Fs", C.c_double)]
 
 
+class SyncParams(C.Structure):
+    """ssf_sync_params (include/ssf.h)."""
+    _fields_ = [("n_rx", C.c_int64), ("n_tx", C.c_int64), ("nModes", C.c_int32), ("SpS", C.c_int32), ("mode", C.c_int32),
+                ("rx_dtype", C.c_int32), ("tx_dtype", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SyncResult(C.Structure):
+    """ssf_sync_result (include/ssf.h)."""
+    _fields_ = [("delay", C.c_int64 * 8), ("swap", C.c_int32 * 8), ("rot", C.c_int32 * 8), ("conj", C.c_int32 * 8),
+                ("corrMatrix", C.c_double * 64)]
+
+
+SYNC_MODES = {"amp": 0, "real": 1}                                                          # ssf_sync_mode
+SYNC_ROT = (1, -1, 1j, -1j)                                                                 # ssf_sync_result.rot
+SYNC_MAX_MODES = 8
+
+
 class EqStage(C.Structure):
     """ssf_eq_stage (include/ssf.h)."""
     _fields_ = [("L", C.c_int64), ("alg", C.c_int32), ("reserved", C.c_int32), ("mu", C.c_double)]
@@ -202,6 +219,9 @@ SYMBOLS = {
                           C.c_void_p]),
     "ssf_foe": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p,
                           C.POINTER(C.c_double)]),
+    "ssf_symbol_sync": (C.c_int, [C.c_int, C.POINTER(SyncParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(SyncResult)]),
+    "ssf_finddelay": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "ssf_sync_transform_time": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_mimo_eq": (C.c_int, [C.c_int, C.POINTER(EqParams), C.POINTER(EqStage), C.POINTER(C.c_double), C.POINTER(C.c_double),
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssf_calc_llr": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32),

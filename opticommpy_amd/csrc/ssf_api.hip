@@ -774,6 +774,45 @@ int ssf_foe(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t P, dou
     return rc ? set_err(rc, "ssf_foe: " + err) : SSF_OK;
 }
 
+// ---- sequence synchronisation (engine_sync.hip)
+int ssf_symbol_sync(int device, const ssf_sync_params *p, const void *rx, const void *tx, void *out, ssf_sync_result *result) {
+    if (!p || !rx || !tx || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: NULL argument");
+    if (p->mode != SSF_SYNC_AMP && p->mode != SSF_SYNC_REAL) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: mode must be SSF_SYNC_AMP or SSF_SYNC_REAL");
+    if (p->nModes < 1 || p->nModes > 8) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: nModes must be 1 .. 8");
+    if (p->SpS < 1 || p->SpS * p->nModes > 256) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: SpS >= 1 and SpS * nModes <= 256");
+    if (p->n_rx < 1 || p->n_rx % p->SpS) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: the length of rx is not a multiple of SpS");
+    if (p->n_tx < 2 || p->n_rx / p->SpS < 2) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: at least 2 symbols on either side");
+    if (p->n_tx > (1LL << 31) || p->n_rx > (1LL << 31)) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: at most 2^31 rows");
+    for (int32_t d : {p->rx_dtype, p->tx_dtype})
+        if (d != SSF_M_C128 && d != SSF_M_C64) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: dtype must be complex128 or complex64");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::sync_run(device, p, rx, tx, out, result, &err);
+    return rc ? set_err(rc, "ssf_symbol_sync: " + err) : SSF_OK;
+}
+
+int ssf_finddelay(int device, int64_t nx, int64_t ny, int32_t x_dtype, int32_t y_dtype, const void *x, const void *y, int64_t *delay_out) {
+    if (!x || !y || !delay_out) return set_err(SSF_ERR_BAD_ARG, "ssf_finddelay: NULL argument");
+    if (nx < 1 || ny < 1 || nx > (1LL << 31) || ny > (1LL << 31)) return set_err(SSF_ERR_BAD_ARG, "ssf_finddelay: lengths must be 1 .. 2^31");
+    for (int32_t d : {x_dtype, y_dtype})
+        if (d < SSF_M_C128 || d > SSF_M_F32) return set_err(SSF_ERR_BAD_ARG, "ssf_finddelay: unknown dtype");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::sync_finddelay(device, nx, ny, x_dtype, y_dtype, x, y, delay_out, &err);
+    return rc ? set_err(rc, "ssf_finddelay: " + err) : SSF_OK;
+}
+
+int ssf_sync_transform_time(int device, int64_t L, int32_t nseq, int32_t nslots, int32_t nslots2, int32_t reps, double *seconds_out) {
+    if (!seconds_out) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_transform_time: NULL argument");
+    if (L < 4 || L > (1LL << 32) || (L & (L - 1))) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_transform_time: L must be a power of two, 4 .. 2^32");
+    if (nseq < 1 || nseq > 24 || nslots < 1 || nslots > 64 || nslots2 < 0 || nslots2 > nslots || reps < 1 || reps > 1000)
+        return set_err(SSF_ERR_BAD_ARG, "ssf_sync_transform_time: 1 <= nseq <= 24, 0 <= nslots2 <= nslots <= 64, 1 <= reps <= 1000");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::sync_transform_time(device, L, nseq, nslots, nslots2, reps, seconds_out, &err);
+    return rc ? set_err(rc, "ssf_sync_transform_time: " + err) : SSF_OK;
+}
+
 // ---- adaptive MIMO equalizer (engine_eq.hip): every check comes before the first allocation or launch
 static const char *eq_bad(const ssf_eq_params *p, const ssf_eq_stage *st, const void *ref) {
     if (p->nModes < 1 || p->nModes > 4) return "nModes must be 1 .. 4";

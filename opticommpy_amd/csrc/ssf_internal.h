@@ -166,6 +166,11 @@ int cpr_bps(int device, int64_t n, int nModes, int dtype, int Nh, int B, int M, 
             std::string *err);
 int cpr_foe(int device, int64_t n, int nModes, int dtype, int P, double Fs, const void *x, void *sig_out, double *fo_out,
             std::string *err);
+// engine_sync.hip (arguments already checked by ssf_api.hip)
+int sync_run(int device, const ssf_sync_params *p, const void *rx, const void *tx, void *out, ssf_sync_result *res, std::string *err);
+int sync_finddelay(int device, int64_t nx, int64_t ny, int x_dtype, int y_dtype, const void *x, const void *y, int64_t *delay_out,
+                   std::string *err);
+int sync_transform_time(int device, int64_t L, int nseq, int nslots, int nslots2, int reps, double *seconds_out, std::string *err);
 // engine_eq.hip (arguments already checked by ssf_api.hip)
 int eq_run(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const double *table, const double *radii, void *H_inout,
            const void *x, const void *ref, void *sig_out, double *errsq_out, std::string *err);
