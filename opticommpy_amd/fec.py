@@ -22,6 +22,7 @@ Scope and limits (anything else raises ``ValueError`` before the library is load
   ``readAlist`` returns), or a dense 0/1 array.  scipy is not needed.  The edges of a check are taken in ascending column index;
 * ``param.alg`` 'SPA' or 'MSA'; ``param.prec`` float32 (the default) or float64; ``param.maxIter`` >= 1 (default 25);
 * ``n_ <= n`` (``n_ < n``: the last ``n - n_`` variables are punctured), every check degree 1 .. 64, every variable degree <= 64;
+  a check of degree 1 under MSA yields infinite messages (and NaN back on that edge, taken as negative), as in the reference;
 * ``calcLLR``: ``M`` a power of two, 2 .. 1024, ``bitMap`` of shape ``(M, log2 M)`` with entries 0 and 1.
 
 Deviations from the reference, on purpose:

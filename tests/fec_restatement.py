@@ -5,7 +5,8 @@ taken in the reference's order and in ``prec``:
 
 * the edges of check ``c`` are its columns in ascending order; a variable sums ``llr + sum C->V`` over its edges in ascending
   check index, left to right, and sends that sum minus the edge's own message;
-* MSA: first minimum (strict ``<``), second minimum, product of signs with ``val >= 0 -> +1``: bit-equal to the reference;
+* MSA: first minimum (strict ``<``), second minimum, product of signs with ``val >= 0 -> +1`` and anything else, NaN included,
+  ``-1`` (fec.py:609, 622): bit-equal to the reference.  A check of degree 1 sends +-inf, its variable answers ``inf - inf``;
 * SPA: for every edge the product of ``tanh(x / 2)`` over the check's other edges in ascending order starting from 1.0 (the
   reference's O(d_c^2) product), clipped to +-0.999999 where the message is 2 atanh(0.999999) evaluated in double, ``2 atanh``
   otherwise.  The device forms the same products from prefix and suffix products: another rounding.
@@ -90,7 +91,7 @@ def decode(indptr, indices, shape, llrs, alg="SPA", maxIter=25, prec=np.float32)
                 ok = cvalid[:, j, None]
                 val = x[cidx[:, j]]
                 mag = np.abs(val)
-                sign = np.where(ok & (val < 0), -sign, sign)
+                sign = np.where(ok & ~(val >= 0), -sign, sign)            # fec.py:609: 1 if val >= 0 else -1, so NaN is negative
                 lower = ok & (mag < min1)
                 second = ok & ~lower & (mag < min2)
                 min2 = np.where(lower, min1, np.where(second, mag, min2))

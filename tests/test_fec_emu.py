@@ -2,7 +2,8 @@
 opticommpy_amd/csrc/fec_kernels.h -- the node bodies the gfx950 kernels call -- and walks them over nodes and codewords with g++
 as the two engines of engine_fec.hip do (padded per-codeword messages and a loop left at convergence; messages of all codewords
 with the unsat / done flags of the launches).  Every fixture is held to the bounds of tests/fec_cases.py in both precisions and
-from both walks, which must agree bit for bit."""
+from both walks, which must agree bit for bit; so is every row of tests/fec_shape_cases.py marked for the emulator, against the
+restatement."""
 import os
 import subprocess
 
@@ -11,6 +12,7 @@ import pytest
 
 import fec_cases as fc
 import fec_restatement as fr
+import fec_shape_cases as fs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -68,13 +70,11 @@ def test_a_float32_input_is_clipped_then_widened(emu, tmp_path):
 @pytest.mark.parametrize("dc", [3, 9, 33, 64])
 def test_emulated_check_degrees_match_the_restatement(emu, tmp_path, dc):
     """One graph per form of the SPA check body (unrolled to 8, to 32, the loop) with irregular degrees up to ``dc``, and the
-    variable degrees that follow; float64 at the bound of the fixtures, MSA bit-equal.  (No check of degree 1: min-sum answers it
-    with an infinite message, in the reference too.)"""
+    variable degrees that follow; float64 at the bound of the fixtures, MSA bit-equal."""
     rng = np.random.default_rng(dc)
     m, n = 40, 160
-    rows = [np.sort(rng.choice(n, size=int(d), replace=False)) for d in np.r_[dc, 2, rng.integers(2, dc + 1, size=m - 2)]]
-    indptr = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int32)
-    indices = np.concatenate(rows).astype(np.int32)
+    indptr, indices = fs.sampled_graph(rng, m, n, (dc, 2), 2, dc)
+    assert np.diff(indptr)[0] == dc and np.diff(indptr).max() == dc and np.diff(indptr).min() == 2
     llrs = 2 * (1 + 0.8 * rng.normal(size=(n, 3))) / 0.64
     for alg in ("SPA", "MSA"):
         prm = fc.Param(H=fc.Csr(indptr, indices, (m, n)), alg=alg, maxIter=5, prec=np.float64)
@@ -86,6 +86,29 @@ def test_emulated_check_degrees_match_the_restatement(emu, tmp_path, dc):
                 assert np.array_equal(out, want[1]), (dc, engine)
             else:
                 assert np.all(fc.rel_cols(out, want[1]) <= fc.REL), (dc, engine, fc.rel_cols(out, want[1]))
+
+
+@pytest.mark.parametrize("row", fs.EMU_ROWS, ids=lambda r: r.id)
+def test_emulated_shape_row_matches_the_restatement(emu, tmp_path, row):
+    """Every size, degree and edge of tests/fec_shape_cases.py from both walks, one of them in the other orientation."""
+    fs.check_conditions(row)
+    x = fs.signals(row)
+    lds = run_emu(emu, tmp_path, x, fs.param(row), "lds")
+    fs.compare(row, lds, "emulated, lds")
+    bits, out, fail, last = run_emu(emu, tmp_path, np.ascontiguousarray(x.T), fs.param(row), "global", transposed=True)
+    for a, b in zip((bits.T, out.T, fail, last), lds):
+        assert a.dtype == b.dtype and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes(), row.id
+
+
+@pytest.mark.parametrize("row", fs.EMU_LLR_ROWS, ids=lambda r: r.id)
+def test_emulated_llr_shape_row_matches_the_restatement(emu, tmp_path, row):
+    fs.check_llr_conditions(row)
+    g = fs.llr_signals(row)
+    q = fc.write_emu_llr(tmp_path / "in.bin", g)
+    subprocess.check_call([emu, "llr", str(tmp_path / "in.bin"), str(tmp_path / "out.bin")])
+    got = np.fromfile(tmp_path / "out.bin", dtype=np.float64)
+    assert got.shape == (row.n * q["b"],)
+    fs.compare_llr(row, got, "emulated")
 
 
 @pytest.mark.parametrize("name", fc.LLR_CASES)

@@ -13,6 +13,7 @@ import pytest
 import fec_cases as fc
 import fec_restatement as fr
 import opticommpy_amd as oa
+from fec_shape_cases import regular_code
 from opticommpy_amd import _lib, device
 
 pytestmark = pytest.mark.gpu
@@ -91,30 +92,6 @@ def test_reading_the_flags_early_changes_nothing():
         fc.compare_decode(want, g, g["cfg"]["prec"], name)
         for every in (1, 2, 7):
             same_bits(decode(g["llrs"], fc.param(g, engine="global", syncEvery=every)), want, (name, every))
-
-
-def regular_code(n, seed):
-    """CSR of a seeded random (3, 6)-regular parity-check matrix with n variables: three layers, each a permutation of the
-    variables dealt two to a check; a variable that meets itself in a check is swapped away until none does."""
-    rng = np.random.default_rng(seed)
-    m = n // 2
-    layers = np.stack([rng.permutation(n) for _ in range(3)])           # check c gets layers[:, 2 c] and layers[:, 2 c + 1]
-    for _ in range(100):
-        cols = layers.reshape(3, m, 2).transpose(1, 0, 2).reshape(m, 6)
-        s = np.sort(cols, axis=1)
-        bad = np.flatnonzero(np.any(s[:, 1:] == s[:, :-1], axis=1))
-        if not len(bad):
-            break
-        for c in bad:                                                    # move the check's entries of two layers elsewhere
-            for layer in (1, 2):
-                for k in (2 * c, 2 * c + 1):
-                    o = int(rng.integers(0, n))
-                    layers[layer, k], layers[layer, o] = layers[layer, o], layers[layer, k]
-    else:
-        raise AssertionError("no simple graph found")
-    cols = np.sort(cols, axis=1)
-    assert np.all(np.bincount(cols.reshape(-1), minlength=n) == 3)
-    return fc.Csr(np.arange(0, 6 * m + 1, 6, dtype=np.int32), cols.reshape(-1).astype(np.int32), (m, n))
 
 
 def noisy_zero_codewords(n, snrs_dB, seed):

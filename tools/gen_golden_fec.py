@@ -19,6 +19,10 @@ Decoding fixtures ``ldpc_<case>.npz``, four codewords each, all-zero codeword ov
     cfg                      JSON: alg, maxIter, prec (the precision the case is named for), snr_dB, seed, table, numpy version
 ``ldpc_graph_<table>.npz``: the edge maps check_offsets, var_offsets, var_edge_indices the reference builds at fec.py:388-411,
 taken from the locals of its own run, with H's CSR.
+``edge_msa_deg1.npz``, ``edge_spa_deg1.npz``: the fields of a decoding fixture but ``amp`` on a seeded irregular m = 12, n = 24 graph
+with one check of degree 1 and one variable of degree 0, maxIter 6.  Asserted: the min-sum fixture holds an infinite posterior,
+the two precisions agree on frameErrors, lastIter, the NaN positions and the bits elsewhere, codewords fail next to one that
+converges after iteration 0.
 ``llr_<case>.npz``: rxSymb, sigma2, constSymb, bitMap, px and the reference's LLRs.
 
 Conditions asserted here, re-asserted by tests/fec_cases.py:check_conditions, so that no fixture lets a test pass emptily:
@@ -264,6 +268,63 @@ def generate_llr(name):
           f"{int(np.sum(np.isinf(llr)))} infinite", flush=True)
 
 
+EDGE_CASES = {"edge_msa_deg1": "MSA", "edge_spa_deg1": "SPA"}
+EDGE_M, EDGE_N, EDGE_MAXITER, EDGE_GRAPH_SEED, EDGE_SIGMA2 = 12, 24, 6, 5, 0.5
+
+
+def edge_graph():
+    """scipy CSR of the m = 12, n = 24 edge graph: check 0 has degree 1 (variable 3, which other checks hold too, so that its infinite
+    posterior travels), variable 23 has degree 0, the other checks have 2 .. 6 distinct variables of 0 .. 22 and every one of those
+    is in a check."""
+    import scipy.sparse
+    rng = np.random.default_rng(EDGE_GRAPH_SEED)
+    rows = [np.array([3])]
+    for d in rng.integers(2, 7, size=EDGE_M - 1):
+        rows.append(np.sort(rng.choice(EDGE_N - 1, size=int(d), replace=False)))
+    indptr = np.concatenate(([0], np.cumsum([len(r) for r in rows])))
+    indices = np.concatenate(rows)
+    H = scipy.sparse.csr_matrix((np.ones(len(indices), dtype=np.int8), indices, indptr), shape=(EDGE_M, EDGE_N))
+    dv = np.bincount(indices, minlength=EDGE_N)
+    assert np.diff(indptr).min() == 1 and np.sum(np.diff(indptr) == 1) == 1 and np.sum(dv == 0) == 1 and dv[EDGE_N - 1] == 0 and dv[3] >= 2
+    return H
+
+
+def generate_edge(name):
+    """``<name>.npz`` (no ``ldpc_`` prefix: not one of the nine cases): the fields of a decoding fixture but ``amp``, on the
+    edge graph.  Min-sum answers the check of degree 1 with an infinite message and gets ``inf - inf`` back, so out64 / out32 hold
+    +-inf and may hold NaN; bits32 / bits64 are meaningful where the posterior is not NaN."""
+    alg = EDGE_CASES[name]
+    H = edge_graph()
+    for seed in range(1, 200):
+        rng = np.random.default_rng(seed)
+        llrs = 2 * (1 + np.sqrt(EDGE_SIGMA2) * rng.normal(size=(EDGE_N, NWORDS))) / EDGE_SIGMA2
+        with np.errstate(invalid="ignore"):
+            out64, bits64, fail64, iter64 = reference_decode(H, llrs, alg, EDGE_MAXITER, "float64")
+            out32, bits32, fail32, iter32 = reference_decode(H, llrs, alg, EDGE_MAXITER, "float32")
+        same = np.array_equal(fail32, fail64) and np.array_equal(iter32, iter64) and \
+            np.array_equal(bits32[~np.isnan(out64)], bits64[~np.isnan(out64)]) and np.array_equal(np.isnan(out32), np.isnan(out64))
+        if same and 0 < fail64.sum() < NWORDS and np.any((fail64 == 0) & (iter64 > 0)):
+            break
+    else:
+        raise SystemExit(f"{name}: no seed gives failed codewords next to one that converges after iteration 0")
+    assert np.any(np.isinf(out64)) == (alg == "MSA") and np.any(np.isinf(out32)) == (alg == "MSA"), name
+    if alg == "SPA":
+        assert np.all(np.isfinite(out64)) and np.all(np.isfinite(out32))
+        self_err = rel_cols(out32, out64)
+    else:
+        self_err = np.zeros(NWORDS)
+    cfg = dict(name=name, alg=alg, maxIter=EDGE_MAXITER, prec="float64", sigma2=EDGE_SIGMA2, seed=seed, graph_seed=EDGE_GRAPH_SEED,
+               n=EDGE_N, m=EDGE_M, n_=EDGE_N, numpy=np.__version__)
+    os.makedirs(OUT, exist_ok=True)
+    path = os.path.join(OUT, f"{name}.npz")
+    np.savez_compressed(path, indptr=H.indptr.astype(np.int32), indices=H.indices.astype(np.int32), shape=np.array(H.shape), n_=EDGE_N,
+                        llrs=llrs, out64=out64, bits64=bits64, fail64=fail64, iter64=iter64, out32=out32, bits32=bits32,
+                        fail32=fail32, iter32=iter32, self_err=self_err, cfg=json.dumps(cfg))
+    assert os.path.getsize(path) <= MAX_BYTES
+    print(f"{name}: {os.path.getsize(path)} bytes  seed {seed}  frameErrors {fail64.tolist()}  lastIter {iter64.tolist()}  "
+          f"{int(np.sum(np.isinf(out64)))} infinite, {int(np.sum(np.isnan(out64)))} NaN posteriors", flush=True)
+
+
 def check_set():
     fails, iters = [], []
     for name in CASES:
@@ -274,9 +335,11 @@ def check_set():
 
 
 if __name__ == "__main__":
-    todo = sys.argv[1:] or [f"graph:{k}" for k in TABLES] + [f"llr:{k}" for k in LLR_CASES] + list(CASES)
+    todo = sys.argv[1:] or [f"graph:{k}" for k in TABLES] + [f"llr:{k}" for k in LLR_CASES] + list(CASES) + list(EDGE_CASES)
     for case in todo:
-        if case.startswith("graph:"):
+        if case in EDGE_CASES:
+            generate_edge(case)
+        elif case.startswith("graph:"):
             generate_graph(case[6:])
         elif case.startswith("llr:"):
             generate_llr(case[4:])
