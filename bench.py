@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- SSFM steps/s on MI355X for BASELINE.json's configurations.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the K steps, writes the outputs if
+--dump-outputs is given and prints the result line.  --full adds, after the timed steps and outside them, everything else this
+file measures or checks: the parity gate of the run (CPU oracle with its cpu_baseline, or a reference-generated fixture), the
+per-kernel HIP-event pass, the measured copy ceiling of the roofline and, for the default configuration on one GPU, the "also"
+legs (configs 3, 2 out of cache, 4, 5, 1 x 16, the receiver chain, the reference notebook's benchmark).  --parity, --cpu-steps,
+--no-cpu-baseline, --no-kernel-times and --no-also choose among those and mean nothing without --full.
 
 --dump-outputs DIR: the output field of every unit after the K timed steps, as DIR/unit<u>.npy (float64 / float32 [real, imag]
 pairs; at most 64 MB in all, a fixed seeded sample of sample positions beyond that -- dump_outputs).  The inputs are seeded: the
@@ -27,7 +34,7 @@ inputs of ALL units and scatters them (ncclSend / ncclRecv), barriers and the ma
 per-unit output checksums are all-gathered.  No per-step communication.  Units of a rank run on two
 lanes (plan + stream + host thread each) so that one unit's row launches overlap the other's column launches.
 
-Prints ONE JSON line on rank 0; exits non-zero if the in-run parity check against the CPU oracle fails.
+Prints ONE JSON line on rank 0; with --full, exits non-zero if the in-run parity check against the CPU oracle fails.
 """
 import argparse
 import ctypes as C
@@ -211,7 +218,8 @@ def self_launch(n):
 
 def measure(env, cfg, m):
     """One configuration: synthesise / scatter the inputs, warm up, time EXACTLY m.steps steps per unit, gather the per-unit
-    checksums, and (rank 0) build the record with the roofline, the per-kernel pass and the parity leg m.parity asks for.
+    checksums, and (rank 0) build the record with the roofline and, under m.full, the per-kernel pass, the copy probe and the
+    parity leg m.parity asks for.
     -> (rec or None, ok)"""
     lib, _lib, mgpu, comm, comm_name = env.lib, env._lib, env.mgpu, env.comm, env.comm_name
     rank, world, local_rank = env.rank, env.world, env.local_rank
@@ -388,7 +396,7 @@ def measure(env, cfg, m):
 
         # per-kernel timing pass (HIP events around every launch; separate from the headline run because the events
         # themselves cost a few microseconds per launch)
-        if not m.no_kernel_times and w["model"] == "manakov" and lib.ssf_set_profiling(plans[u0], 1) == 0:
+        if m.full and not m.no_kernel_times and w["model"] == "manakov" and lib.ssf_set_profiling(plans[u0], 1) == 0:
             nprof = min(m.steps, 200)
             _lib.raise_for(lib, plans[u0], lib.ssf_upload(plans[u0], dev_in[u0]))
             stp = {}
@@ -428,7 +436,7 @@ def measure(env, cfg, m):
         # measured memory ceiling on this box: a kernel with the row stage's memory shape and no arithmetic
         probe = C.c_double(0.0)
         probe_bytes = max(65536, (2 * s * N) // 65536 * 65536)
-        if lib.ssf_device_copy_bandwidth(local_rank, probe_bytes, 50, C.byref(probe)) == 0:
+        if m.full and lib.ssf_device_copy_bandwidth(local_rank, probe_bytes, 50, C.byref(probe)) == 0:
             rec["roofline"]["measured_copy_GBs"] = probe.value
             rec["roofline"]["frac_of_measured_copy"] = achieved / probe.value
             rec["roofline"]["measured_copy_note"] = ("burst copy kernel, %d MiB read + %d MiB written per launch, no arithmetic"
@@ -451,7 +459,8 @@ def measure(env, cfg, m):
                 pass
 
         # ---- parity gate of the run: the CPU oracle (+ cpu_baseline on one GPU), or a reference-generated fixture
-        if m.parity == "oracle":
+        parity = m.parity if m.full else "none"              # (a plain run: the headline figure only)
+        if parity == "oracle":
             n = m.cpu_steps or {16: 100, 20: 16, 22: 6}.get(w["log2n"], 8)
             if world > 1:
                 n = min(n, 4)
@@ -486,7 +495,7 @@ def measure(env, cfg, m):
                                                  % (n, os.cpu_count(), cpu_model, np.__version__),
                                        "iterations_per_step": it_cpu / n}
                 rec["speedup_vs_cpu"] = rec["value"] / (n / tc)
-        elif m.parity == "fixture_cfg3":
+        elif parity == "fixture_cfg3":
             # tests/golden/wl_cfg3_n22.npz: the REFERENCE on config 3's own field (2^22, seed 3) for six steps, complex128 and
             # complex64 (tools/gen_golden.py cfg3): decimated output + a seeded projection of the whole output
             z = np.load(os.path.join(ROOT, "tests", "golden", "wl_cfg3_n22.npz"))
@@ -509,7 +518,7 @@ def measure(env, cfg, m):
             rec["parity"] = {"rel_l2_vs_reference_c128": err, "projection_err": perr, "steps": n, "iterations_gpu": it_gpu,
                              "iterations_reference": it_ref, "gate": gate, "ok": ok,
                              "what": "reference-generated fixture tests/golden/wl_cfg3_n22.npz (decimated output + seeded projection)"}
-        elif m.parity == "fixture_units":
+        elif parity == "fixture_units":
             # tests/golden/wl_units45_n20.npz: every unit of configs 4 / 5 through the REFERENCE for eight steps
             z = np.load(os.path.join(ROOT, "tests", "golden", "wl_units45_n%d.npz" % w["log2n"]))
             fc = json.loads(str(z["cfg"]))
@@ -790,6 +799,9 @@ def main():
     ap.add_argument("--dbp-hz", type=float, default=0.08)
     ap.add_argument("--lanes", type=int, default=int(os.environ.get("SSF_MGPU_LANES", "2")))
     ap.add_argument("--engine", default=os.environ.get("SSF_ENGINE", "auto"))
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what the headline figure does not need: the parity gate (with the CPU baseline), "
+                         "the per-kernel pass, the copy-bandwidth probe and the 'also' legs; the options below down to --parity choose among those")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=0, help="steps of the CPU oracle leg (0: sized for ~10-20 s)")
     ap.add_argument("--no-kernel-times", action="store_true", help="skip the per-kernel HIP-event pass")
@@ -838,7 +850,7 @@ def main():
     m = argparse.Namespace(**vars(args))
     m.nfields, m.parity = 1, (args.parity or ("none" if args.no_cpu_baseline else "oracle"))
     rec, ok = measure(env, int(args.config), m)
-    if rec is not None and world == 1 and int(args.config) == 2 and not (args.log2n or args.prec or args.no_also):
+    if rec is not None and args.full and world == 1 and int(args.config) == 2 and not (args.log2n or args.prec or args.no_also):
         rec["also"] = also_configs(env, args)
     if comm is not None:
         flag = comm.allreduce(np.array([0.0 if ok else 1.0]), "max")     # rank 0 arrives after its extra passes

@@ -65,3 +65,24 @@ def test_bench_dumps_the_timed_steps_output_identically_from_run_to_run(tmp_path
     pw, pr = bench.unit_checksum(a[..., 0] + 1j * a[..., 1])
     assert pw == pytest.approx(recs[0]["unit_checksums"][0][0], rel=1e-12)
     assert pr == pytest.approx(recs[0]["unit_checksums"][0][1], rel=1e-12)
+
+
+@pytest.mark.gpu
+def test_a_plain_run_reports_the_headline_only_and_full_adds_the_rest():
+    """Without --full: set-up, warm-up, the timed steps and the result line, whose headline keys are there -- no parity leg, no CPU
+    baseline, no per-kernel pass, no copy probe, no "also" legs.  With --full (here at 2^14, where no "also" leg runs) they are back
+    and the parity gate decides the exit status; the headline keys say the same in both."""
+    plain_r, plain = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--log2n", "14"], timeout=600)
+    full_r, full = _bench(["--gpus", "1", "--steps", "5", "--warmup", "2", "--log2n", "14", "--full"], timeout=600)
+    assert plain_r.returncode == 0, plain_r.stderr.decode(errors="replace")[-2000:]
+    assert full_r.returncode == 0, full_r.stderr.decode(errors="replace")[-2000:]
+    for rec in (plain, full):
+        assert rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["unit"] == "steps/s" and rec["higher_is_better"] is True
+        assert rec["dtype"] == "f64" and rec["steps"] == 5 and rec["warmup"] == 2 and rec["config"]["unit_steps_total"] == 5
+        assert rec["value"] == pytest.approx(1e3 / rec["ms_per_step"], rel=1e-9)
+    assert plain["metric"] == full["metric"] and plain["unit_checksums"] == full["unit_checksums"]
+    for key in ("parity", "cpu_baseline", "speedup_vs_cpu", "also"):
+        assert key not in plain, key
+    assert "kernels" not in plain["roofline"] and "measured_copy_GBs" not in plain["roofline"]
+    assert full["parity"]["ok"] and full["cpu_baseline"]["value"] > 0
+    assert full["roofline"]["kernels"]["profiled_steps"] == 5 and full["roofline"]["measured_copy_GBs"] > 0

@@ -86,7 +86,7 @@ def test_bench_ranks_over_rccl_configs_4_and_5(ranks, cfg, units):
     """bench.py --gpus N --config 4 / 5 as the driver runs them: rccl_ranks == N, rank 0 synthesises and scatters all units
     (ncclSend / ncclRecv), checksums all-gathered (ncclAllGather): every unit is the reference's."""
     from test_round3 import _bench, _check_units_against_the_reference
-    r, rec = _bench(["--gpus", str(ranks), "--config", cfg, "--steps", "8", "--warmup", "2", "--log2n", "16", "--no-kernel-times"],
+    r, rec = _bench(["--gpus", str(ranks), "--config", cfg, "--steps", "8", "--warmup", "2", "--log2n", "16", "--no-kernel-times", "--full"],
                     _comm_env())
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     assert rec["n_gpus"] == ranks
@@ -99,7 +99,7 @@ def test_bench_ranks_over_rccl_configs_4_and_5(ranks, cfg, units):
 @pytest.mark.parametrize("ranks", _rank_counts())
 def test_bench_ranks_over_rccl_weak_scaling(ranks):
     from test_round3 import _bench
-    r, rec = _bench(["--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--log2n", "16", "--no-kernel-times"], _comm_env())
+    r, rec = _bench(["--gpus", str(ranks), "--steps", "6", "--warmup", "2", "--log2n", "16", "--no-kernel-times", "--full"], _comm_env())
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     _check_comm(rec, ranks)
     assert rec["n_gpus"] == ranks and rec["scaling"] == "weak" and len(rec["unit_checksums"]) == ranks

@@ -103,7 +103,7 @@ def _bench(args, extra_env=None, timeout=600):
 def test_bench_gpus_2_starts_two_ranks_by_itself_config4():
     """`python bench.py --gpus 2 --config 4` with no launcher: two ranks (both on GPU 0 here, over the gloo stand-in, because
     RCCL refuses two ranks on one device), 16 units in two blocks of 8, every unit distinguishable, parity green."""
-    r, rec = _bench(["--gpus", "2", "--config", "4", "--steps", "8", "--warmup", "2", "--log2n", "16", "--no-kernel-times"],
+    r, rec = _bench(["--gpus", "2", "--config", "4", "--steps", "8", "--warmup", "2", "--log2n", "16", "--no-kernel-times", "--full"],
                     dict(SSF_BENCH_DEVICE="mod", SSF_BENCH_COMM="gloo"))
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     assert rec["n_gpus"] == 2 and rec["config"]["units_total"] == 16 and rec["config"]["units_per_gpu"] == 8
@@ -125,7 +125,7 @@ def test_bench_with_three_and_four_ranks_on_the_stand_in(ranks, cfg, units):
     the GPU at five, under the six a shared GPU machine allows (eight ranks on one GPU went over it).
     EVERY unit's (sum |E|^2, <q, E>, iterations) equals the reference's own run of that unit (wl_units45_n16).  No scaling curve
     can be measured this way: the processes share one GPU."""
-    r, rec = _bench(["--gpus", str(ranks), "--config", cfg, "--steps", "8", "--warmup", "2", "--log2n", "16", "--no-kernel-times"],
+    r, rec = _bench(["--gpus", str(ranks), "--config", cfg, "--steps", "8", "--warmup", "2", "--log2n", "16", "--no-kernel-times", "--full"],
                     dict(SSF_BENCH_DEVICE="mod", SSF_BENCH_COMM="gloo"), timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     assert rec["n_gpus"] == ranks and rec["scaling"] == "strong"
@@ -137,7 +137,7 @@ def test_bench_with_three_and_four_ranks_on_the_stand_in(ranks, cfg, units):
 
 @pytest.mark.gpu
 def test_bench_gpus_2_weak_scaling_default_config():
-    r, rec = _bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--log2n", "16", "--no-kernel-times"],
+    r, rec = _bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--log2n", "16", "--no-kernel-times", "--full"],
                     dict(SSF_BENCH_DEVICE="mod", SSF_BENCH_COMM="gloo"))
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     assert rec["n_gpus"] == 2 and rec["scaling"] == "weak" and len(rec["unit_checksums"]) == 2
@@ -419,7 +419,7 @@ def test_configs_4_and_5_at_workload_size_on_one_gpu(cfg, units):
     """BASELINE configs 4 (16 WDM units of 2^20) and 5 (8 units, forward + manakovDBP chained in HBM) at their full unit size,
     all units on this GPU's two lanes (more GPUs only change who owns which block): EVERY unit's checksum and iteration count
     equal to the reference's own run of that unit (reference-generated fixture), in the bench's parity leg and again here."""
-    r, rec = _bench(["--config", cfg, "--steps", "8", "--warmup", "2", "--no-kernel-times", "--parity", "fixture_units"], timeout=900)
+    r, rec = _bench(["--config", cfg, "--steps", "8", "--warmup", "2", "--no-kernel-times", "--parity", "fixture_units", "--full"], timeout=900)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-2000:]
     assert rec["config"]["units_total"] == units and rec["config"]["units_per_gpu"] == units and rec["config"]["lanes_per_gpu"] == 2
     assert rec["parity"]["ok"] and rec["parity"]["units"] == units and rec["parity"]["worst_unit_checksum_err"] <= 1e-9

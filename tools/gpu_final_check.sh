@@ -12,6 +12,6 @@ print(sys.argv[1], round(d["value"], 1), round(d["roofline"]["frac"], 4), "rx ch
       "notebook", {k: round(v["wall_s_device_resident"], 4) for k, v in nb.items()}, "errors", [k for k, v in a.items() if "error" in v])
 PY
 }
-for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd_$i.json 2> $O/driver_cmd_$i.err; summ $O/driver_cmd_$i.json; done
-( time python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real; summ $O/bench_default.json
+for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/driver_cmd_$i.json 2> $O/driver_cmd_$i.err; summ $O/driver_cmd_$i.json; done
+( time python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2>&1 | grep real; summ $O/bench_default.json
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -6

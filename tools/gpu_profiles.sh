@@ -8,8 +8,8 @@ REPO=$PWD
 O=$REPO/gpurun_out/${TAG}_prof/c$CFG; mkdir -p $O
 export TMPDIR=/tmp
 STEPS=$([ $CFG = 2 ] && echo 200 || echo 100)
-python bench.py --config $CFG --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
-python bench.py --config $CFG --no-also --steps $((STEPS * 2)) --warmup 30 > $O/bench.json 2> $O/bench.err
+python bench.py --config $CFG --gpus 1 --steps 20 --warmup 5 --full > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err
+python bench.py --config $CFG --full --no-also --steps $((STEPS * 2)) --warmup 30 > $O/bench.json 2> $O/bench.err
 cd /tmp
 BENCH="python $REPO/bench.py --config $CFG --no-cpu-baseline --no-kernel-times --no-also"
 timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt -- $BENCH --steps $STEPS --warmup 10 > $O/kt.log 2>&1

@@ -7,11 +7,11 @@ cd "$(dirname "$0")/.."
 REPO=$PWD; TAG=${1:-r6}; O=$REPO/gpurun_out/${TAG}_final; mkdir -p $O
 export TMPDIR=/tmp
 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $O/gpu_tests.txt 2>&1; tail -3 $O/gpu_tests.txt
-for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 > $O/driver_cmd_$i.json 2> $O/driver_cmd_$i.err; python - <<PY
+for i in 1 2 3; do python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/driver_cmd_$i.json 2> $O/driver_cmd_$i.err; python - <<PY
 import json; d=json.loads(open("$O/driver_cmd_$i.json").read().strip().splitlines()[-1]); print("driver cmd $i:", round(d["value"],1), round(d["roofline"]["frac"],4), {k: round(v["avg_us"],2) for k,v in d["roofline"]["kernels"].items() if isinstance(v,dict) and "avg_us" in v})
 PY
 done
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; python - <<PY
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; python - <<PY
 import json; d=json.loads(open("$O/bench_default.json").read().strip().splitlines()[-1]); print("default:", round(d["value"],1), round(d["roofline"]["frac"],4), d["cpu_baseline"]["value"]); a=d["also"]
 for k,v in a.items():
     print(" ", k, {x: (round(y,4) if isinstance(y,float) else y) for x,y in v.items() if x in ("value","roofline_frac","ms_per_chain","ms_per_chain_four_calls","error")})
