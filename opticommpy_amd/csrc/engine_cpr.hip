@@ -7,22 +7,19 @@
 //   FOE      x ** P -> rocFFT (plans cached per device, length and mode count) -> first maximum in fftshift order -> derotation
 // No floating-point atomics anywhere: results repeat bit for bit.
 #include <hip/hip_runtime.h>
-#include <rocfft/rocfft.h>
 
-#include <map>
-#include <mutex>
-#include <string>
-#include <tuple>
 #include <vector>
 
+#include "block_reduce.h"
 #include "cpr_kernels.h"
-#include "ssf_internal.h"
+#include "engine_host.h"
 
 namespace ssf {
 namespace {
 using namespace ck;
+using namespace eng;
 
-constexpr int kBlock = 256, kWaves = kBlock / 64, kMaxBlocks = 1024;
+constexpr int kBlock = br::kBlock, kWaves = br::kWaves, kMaxBlocks = 1024;
 constexpr int kSegs = 16;                     // segments a row of minimum distances is cut into for its prefix sums
 constexpr int kMaxChunk = kBlock / kSegs;     // test phases per LDS chunk: one lane per row and segment
 constexpr size_t kLdsBudget = 60 * 1024;      // dynamic LDS of the search per workgroup (64 KiB with the static part: no opt-in needed)
@@ -145,17 +142,6 @@ __global__ __launch_bounds__(kBlock) void k_unwrap_offsets(UnwrapArgs a) {
     }
 }
 
-// one running sum per workgroup -> out[0]
-__device__ void block_sum_store(double v, double *out) {
-    __shared__ double shw[kWaves];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    if (lane == 0) shw[wave] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = ((shw[0] + shw[1]) + shw[2]) + shw[3];
-}
-
 struct ApplyArgs {
     const void *x;
     int dtype, nModes;
@@ -184,17 +170,13 @@ __global__ __launch_bounds__(kBlock) void k_apply(ApplyArgs a) {
         a.y[i] = y;
         acc += y.re * y.re + y.im * y.im;
     }
-    block_sum_store(acc, a.part + blockIdx.x);
+    br::block_sum_store(acc, a.part + blockIdx.x);
 }
 
-// scal[0] = sqrt(mean |y|^2) over all `count` values: one wave, lane-strided then a fixed shuffle tree
+// scal[0] = sqrt(mean |y|^2) over all `count` values, from the nb partial sums: one wave
 __global__ __launch_bounds__(64) void k_norm_fin(const double *part, int nb, long long count, double *scal) {
-    const int lane = threadIdx.x;
-    double s = 0.0;
-    for (int b = lane; b < nb; b += 64) s += part[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_down(s, o, 64);
-    if (lane == 0) scal[0] = sqrt(s / (double)count);
+    const double s = br::wave_sum_partials(part, nb, 1);
+    if (threadIdx.x == 0) scal[0] = sqrt(s / (double)count);
 }
 
 __global__ __launch_bounds__(kBlock) void k_scale(Cplx *y, long long count, const double *scal) {
@@ -283,84 +265,16 @@ __global__ __launch_bounds__(kBlock) void k_foe_derotate(FoeArgs a) {
         a.y[i] = y;
         acc += y.re * y.re + y.im * y.im;
     }
-    block_sum_store(acc, a.part + blockIdx.x);
+    br::block_sum_store(acc, a.part + blockIdx.x);
 }
 
 // ---- host side
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr, cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-};
-struct FftPlan {
-    rocfft_plan plan = nullptr;
-    rocfft_execution_info info = nullptr;
-    void *work = nullptr;
-};
-struct Work {
-    hipStream_t st = nullptr;
+struct Work : WorkBase {
     Buf tables, in, xw, f, phi, phase, loc, bsum, part, scal, cand_m, cand_i, peak, slope, out;
-    std::map<std::pair<long long, int>, FftPlan> plans;
+    FftPlans plans;
     std::vector<double> host_tab, host_slope;     // sources of asynchronous uploads: they outlive the call
 };
-std::mutex g_mu;
-std::map<int, Work> g_work;
-std::once_flag g_fft_once;
-
-size_t elem_size(int dtype) { return dtype == mk::kC128 ? 16 : 8; }
-
-struct Call {
-    Work *w = nullptr;
-    std::string *err;
-    int rc = SSF_OK;
-    bool ok(hipError_t e, const char *what) {
-        if (e == hipSuccess) return true;
-        rc = e == hipErrorOutOfMemory ? SSF_ERR_OOM : SSF_ERR_HIP;
-        *err = std::string(what) + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return false;
-    }
-    bool fft_fail(const char *what) {
-        rc = SSF_ERR_FFT, *err = what;
-        return false;
-    }
-    bool begin(int device) {
-        if (!ok(hipSetDevice(device), "hipSetDevice")) return false;
-        w = &g_work[device];
-        if (!w->st && !ok(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking), "hipStreamCreate")) return false;
-        return true;
-    }
-    bool need(Buf &b, size_t bytes) { return ok(b.need(bytes), "hipMalloc"); }
-    const void *input(const void *p, size_t bytes) {
-        if (on_device(p)) return p;
-        if (!need(w->in, bytes)) return nullptr;
-        if (!ok(hipMemcpyAsync(w->in.p, p, bytes, hipMemcpyHostToDevice, w->st), "hipMemcpy")) return nullptr;
-        return w->in.p;
-    }
-    // where a result is computed: the caller's device memory, or `stage` when the caller's pointer is host memory (or NULL)
-    void *target(void *user, Buf &stage, size_t bytes) {
-        if (user && on_device(user)) return user;
-        return need(stage, bytes) ? stage.p : nullptr;
-    }
-    bool deliver(void *user, const void *dev, size_t bytes) {
-        if (!user || user == dev) return true;
-        return ok(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, w->st), "hipMemcpy");
-    }
-    bool launched() { return ok(hipGetLastError(), "kernel launch"); }
-    bool sync() { return ok(hipStreamSynchronize(w->st), "hipStreamSynchronize"); }
-};
-
-int grid_blocks(long long count) {
-    const long long nb = (count + kBlock - 1) / kBlock;
-    return (int)(nb < kMaxBlocks ? nb : kMaxBlocks);
-}
+using Call = CallT<Work>;
 
 // the table as the product of its real and imaginary levels, if it is one (square QAM): 2 sqrt(M) comparisons per distance
 bool separable(const double *tab, int M, std::vector<double> &lre, std::vector<double> &lim) {
@@ -414,49 +328,22 @@ bool run_bps(Call &c, const void *x, int dtype, long long n, int nModes, int Nh,
     return c.launched();
 }
 
-bool get_plan(Call &c, long long n, int nModes, FftPlan **out) {
-    Work &w = *c.w;
-    std::call_once(g_fft_once, [] { rocfft_setup(); });
-    FftPlan &p = w.plans[{n, nModes}];
-    if (!p.plan) {
-        const size_t len = (size_t)n;
-        if (rocfft_plan_create(&p.plan, rocfft_placement_inplace, rocfft_transform_type_complex_forward, rocfft_precision_double, 1, &len,
-                               (size_t)nModes, nullptr) != rocfft_status_success) {
-            p.plan = nullptr;
-            return c.fft_fail("rocfft_plan_create failed");
-        }
-        size_t ws = 0;
-        rocfft_plan_get_work_buffer_size(p.plan, &ws);
-        if (rocfft_execution_info_create(&p.info) != rocfft_status_success) return c.fft_fail("rocfft_execution_info_create failed");
-        if (ws) {
-            if (!c.ok(hipMalloc(&p.work, ws), "hipMalloc")) return false;
-            rocfft_execution_info_set_work_buffer(p.info, p.work, ws);
-        }
-        rocfft_execution_info_set_stream(p.info, w.st);
-    }
-    *out = &p;
-    return true;
-}
-
 // x (device) -> y = x exp(-j 2 pi fo k / Fs) (device, may not alias x), fo[nModes] to the host; partial sums of |y|^2 in w.part
 bool run_foe(Call &c, const void *x, int dtype, long long n, int nModes, int P, double Fs, Cplx *y, double *fo, int *nb_out) {
     Work &w = *c.w;
     FoeArgs a{};
     a.x = x, a.dtype = dtype, a.nModes = nModes, a.P = P, a.n = n, a.Fs = Fs;
-    a.nb = grid_blocks(n);
-    const int nbf = grid_blocks(n * nModes);
+    a.nb = grid_blocks(n, kBlock, kMaxBlocks);
+    const int nbf = grid_blocks(n * nModes, kBlock, kMaxBlocks);
     if (!c.need(w.f, (size_t)n * nModes * sizeof(Cplx))) return false;
     if (!c.need(w.cand_m, (size_t)nModes * a.nb * sizeof(double)) || !c.need(w.cand_i, (size_t)nModes * a.nb * sizeof(long long))) return false;
     if (!c.need(w.peak, nModes * sizeof(long long)) || !c.need(w.slope, nModes * sizeof(double))) return false;
     if (!c.need(w.part, kMaxBlocks * sizeof(double))) return false;
-    FftPlan *plan = nullptr;
-    if (!get_plan(c, n, nModes, &plan)) return false;
     a.f = (Cplx *)w.f.p, a.cand_m = (double *)w.cand_m.p, a.cand_i = (long long *)w.cand_i.p, a.peak = (long long *)w.peak.p;
     a.slope = (const double *)w.slope.p, a.y = y, a.part = (double *)w.part.p;
     k_foe_pow<<<nbf, kBlock, 0, w.st>>>(a);
     if (!c.launched()) return false;
-    void *io[1] = {w.f.p};
-    if (rocfft_execute(plan->plan, io, nullptr, plan->info) != rocfft_status_success) return c.fft_fail("rocfft_execute failed");
+    if (!transform(c, w.f.p, n, nModes, false)) return false;
     k_foe_argmax<<<dim3(a.nb, nModes), kBlock, 0, w.st>>>(a);
     k_foe_argmax_fin<<<nModes, kBlock, 0, w.st>>>(a);
     if (!c.launched()) return false;
@@ -485,7 +372,7 @@ bool run_norm(Call &c, Cplx *y, long long count, int nb) {
     Work &w = *c.w;
     if (!c.need(w.scal, sizeof(double))) return false;
     k_norm_fin<<<1, 64, 0, w.st>>>((const double *)w.part.p, nb, count, (double *)w.scal.p);
-    k_scale<<<grid_blocks(count), kBlock, 0, w.st>>>(y, count, (const double *)w.scal.p);
+    k_scale<<<grid_blocks(count, kBlock, kMaxBlocks), kBlock, 0, w.st>>>(y, count, (const double *)w.scal.p);
     return c.launched();
 }
 
@@ -493,15 +380,13 @@ bool run_norm(Call &c, Cplx *y, long long count, int nb) {
 
 int cpr_bps(int device, int64_t n, int nModes, int dtype, int Nh, int B, int M, const double *table, const void *x, double *phase_out,
             std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     const size_t ph_bytes = (size_t)n * nModes * sizeof(double);
     double *phase = (double *)c.target(phase_out, w.phase, ph_bytes);
     if (!phase) return c.rc;
-    const void *xd = c.input(x, (size_t)n * nModes * elem_size(dtype));
+    const void *xd = c.input(x, w.in, (size_t)n * nModes * mk::elem_size(dtype));
     if (!xd) return c.rc;
     if (!run_bps(c, xd, dtype, n, nModes, Nh, B, M, table, phase)) return c.rc;
     if (!c.deliver(phase_out, phase, ph_bytes)) return c.rc;
@@ -511,15 +396,13 @@ int cpr_bps(int device, int64_t n, int nModes, int dtype, int Nh, int B, int M, 
 
 int cpr_foe(int device, int64_t n, int nModes, int dtype, int P, double Fs, const void *x, void *sig_out, double *fo_out,
             std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     const size_t out_bytes = (size_t)n * nModes * sizeof(Cplx);
     Cplx *y = (Cplx *)c.target(sig_out, w.out, out_bytes);
     if (!y) return c.rc;
-    const void *xd = c.input(x, (size_t)n * nModes * elem_size(dtype));
+    const void *xd = c.input(x, w.in, (size_t)n * nModes * mk::elem_size(dtype));
     if (!xd) return c.rc;
     int nb = 0;
     if (!run_foe(c, xd, dtype, n, nModes, P, Fs, y, fo_out, &nb)) return c.rc;
@@ -530,10 +413,8 @@ int cpr_foe(int device, int64_t n, int nModes, int dtype, int P, double Fs, cons
 
 int cpr_run(int device, const ssf_cpr_params *p, const double *table, const void *x, void *sig_out, double *phase_out, double *fo_out,
             std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     const long long n = p->n, count = n * p->nModes;
     const int nModes = p->nModes;
@@ -546,7 +427,7 @@ int cpr_run(int device, const ssf_cpr_params *p, const double *table, const void
     if (!c.need(w.phi, ph_bytes) || !c.need(w.loc, ph_bytes) || !c.need(w.bsum, (size_t)nModes * u.nblk * sizeof(double))) return c.rc;
     if (!c.need(w.part, kMaxBlocks * sizeof(double))) return c.rc;
     if (p->runFOE && !c.need(w.xw, out_bytes)) return c.rc;
-    const void *xd = c.input(x, (size_t)count * elem_size(p->dtype));
+    const void *xd = c.input(x, w.in, (size_t)count * mk::elem_size(p->dtype));
     if (!xd) return c.rc;
     int dtype = p->dtype;
     if (p->runFOE) {
@@ -565,7 +446,7 @@ int cpr_run(int device, const ssf_cpr_params *p, const double *table, const void
     ApplyArgs a{};
     a.x = xd, a.dtype = dtype, a.nModes = nModes, a.n = n, a.nblk = u.nblk;
     a.phi = u.phi, a.loc = u.loc, a.boff = u.bsum, a.phase_out = phase, a.y = y, a.part = (double *)w.part.p;
-    const int nb = grid_blocks(count);
+    const int nb = grid_blocks(count, kBlock, kMaxBlocks);
     k_apply<<<nb, kBlock, 0, w.st>>>(a);
     if (!c.launched()) return c.rc;
     if (!run_norm(c, y, count, nb)) return c.rc;

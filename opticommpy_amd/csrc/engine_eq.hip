@@ -10,17 +10,15 @@
 // No communication between waves, no flags, no atomics: every loop's trip count is known at launch and results repeat bit for bit.
 #include <hip/hip_runtime.h>
 
-#include <map>
-#include <mutex>
-#include <string>
 #include <vector>
 
+#include "engine_host.h"
 #include "eq_kernels.h"
-#include "ssf_internal.h"
 
 namespace ssf {
 namespace {
 using namespace eqk;
+using namespace eng;
 
 constexpr int kStaticBlock = 256;
 constexpr int kMaxSegs = 8;                   // segments of one serial launch: they travel as kernel arguments (scalar loads, no
@@ -239,73 +237,19 @@ __global__ __launch_bounds__(kStaticBlock) void k_eq_static(StaticArgs a) {
 }
 
 // ---- host side
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr, cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-};
-struct Work {
-    hipStream_t st = nullptr;
+struct Work : WorkBase {
     Buf in, refin, H, tables, out, esq;
     std::vector<double> host_tab;             // sources of asynchronous uploads: they outlive the call
     std::vector<Seg> host_segs;
 };
-std::mutex g_mu;
-std::map<int, Work> g_work;
-
-struct Call {
-    Work *w = nullptr;
-    std::string *err;
-    int rc = SSF_OK;
-    bool ok(hipError_t e, const char *what) {
-        if (e == hipSuccess) return true;
-        rc = e == hipErrorOutOfMemory ? SSF_ERR_OOM : SSF_ERR_HIP;
-        *err = std::string(what) + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return false;
-    }
-    bool begin(int device) {
-        if (!ok(hipSetDevice(device), "hipSetDevice")) return false;
-        w = &g_work[device];
-        if (!w->st && !ok(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking), "hipStreamCreate")) return false;
-        return true;
-    }
-    bool need(Buf &b, size_t bytes) { return ok(b.need(bytes), "hipMalloc"); }
-    const void *input(const void *p, Buf &stage, size_t bytes) {
-        if (on_device(p)) return p;
-        if (!need(stage, bytes)) return nullptr;
-        if (!ok(hipMemcpyAsync(stage.p, p, bytes, hipMemcpyHostToDevice, w->st), "hipMemcpy")) return nullptr;
-        return stage.p;
-    }
-    void *target(void *user, Buf &stage, size_t bytes) {
-        if (user && on_device(user)) return user;
-        return need(stage, bytes) ? stage.p : nullptr;
-    }
-    bool deliver(void *user, const void *dev, size_t bytes) {
-        if (!user || user == dev) return true;
-        return ok(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, w->st), "hipMemcpy");
-    }
-    bool launched() { return ok(hipGetLastError(), "kernel launch"); }
-    bool sync() { return ok(hipStreamSynchronize(w->st), "hipStreamSynchronize"); }
-};
-
-size_t elem_size(int dtype) { return dtype == mk::kC128 ? 16 : 8; }
+using Call = CallT<Work>;
 
 }  // namespace
 
 int eq_run(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const double *table, const double *radii, void *H_inout,
            const void *x, const void *ref, void *sig_out, double *errsq_out, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     const int nModes = p->nModes, nTaps = p->nTaps;
     const size_t out_bytes = (size_t)p->total * nModes * sizeof(Cplx), esq_bytes = (size_t)p->total * nModes * sizeof(double);
@@ -314,11 +258,11 @@ int eq_run(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const
     double *esq = errsq_out ? (double *)c.target(errsq_out, w.esq, esq_bytes) : nullptr;
     Cplx *H = (Cplx *)c.target(H_inout, w.H, H_bytes);
     if (!y || !H || (errsq_out && !esq)) return c.rc;
-    const void *xd = c.input(x, w.in, (size_t)p->n * nModes * elem_size(p->dtype));
+    const void *xd = c.input(x, w.in, (size_t)p->n * nModes * mk::elem_size(p->dtype));
     if (!xd) return c.rc;
     const void *rd = nullptr;
     if (ref) {
-        rd = c.input(ref, w.refin, (size_t)p->nref * nModes * elem_size(p->ref_dtype));
+        rd = c.input(ref, w.refin, (size_t)p->nref * nModes * mk::elem_size(p->ref_dtype));
         if (!rd) return c.rc;
     }
     if (H != H_inout && !c.ok(hipMemcpyAsync(H, H_inout, H_bytes, hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;

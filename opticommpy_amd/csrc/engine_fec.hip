@@ -18,18 +18,15 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <map>
-#include <mutex>
-#include <string>
 #include <vector>
 
+#include "engine_host.h"
 #include "fec_kernels.h"
-#include "metrics_kernels.h"
-#include "ssf_internal.h"
 
 namespace ssf {
 namespace {
 using namespace fec;
+using namespace eng;
 
 constexpr int kBlock = 256;
 constexpr int kLlrMaxM = 1024;
@@ -195,62 +192,12 @@ __global__ __launch_bounds__(kBlock) void k_finish(DecArgs a, int last, int *d_f
 }
 
 // ---- host side
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr, cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-};
-struct Work {
-    hipStream_t st = nullptr;
+struct Work : WorkBase {
     Buf in, tables, out, bits, fail, iter, msg, llr, post, hard, flags, state;
     std::vector<unsigned char> host_tab;      // source of an asynchronous upload: it outlives the call
     std::vector<int> host_done;
 };
-std::mutex g_mu;
-std::map<int, Work> g_work;
-
-struct Call {
-    Work *w = nullptr;
-    std::string *err;
-    int rc = SSF_OK;
-    bool ok(hipError_t e, const char *what) {
-        if (e == hipSuccess) return true;
-        rc = e == hipErrorOutOfMemory ? SSF_ERR_OOM : SSF_ERR_HIP;
-        *err = std::string(what) + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return false;
-    }
-    bool begin(int device) {
-        if (!ok(hipSetDevice(device), "hipSetDevice")) return false;
-        w = &g_work[device];
-        if (!w->st && !ok(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking), "hipStreamCreate")) return false;
-        return true;
-    }
-    bool need(Buf &b, size_t bytes) { return ok(b.need(bytes), "hipMalloc"); }
-    const void *input(const void *p, Buf &stage, size_t bytes) {
-        if (on_device(p)) return p;
-        if (!need(stage, bytes)) return nullptr;
-        if (!ok(hipMemcpyAsync(stage.p, p, bytes, hipMemcpyHostToDevice, w->st), "hipMemcpy")) return nullptr;
-        return stage.p;
-    }
-    void *target(void *user, Buf &stage, size_t bytes) {
-        if (user && on_device(user)) return user;
-        return need(stage, bytes) ? stage.p : nullptr;
-    }
-    bool deliver(void *user, const void *dev, size_t bytes) {
-        if (!user || user == dev) return true;
-        return ok(hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, w->st), "hipMemcpy");
-    }
-    bool launched() { return ok(hipGetLastError(), "kernel launch"); }
-    bool sync() { return ok(hipStreamSynchronize(w->st), "hipStreamSynchronize"); }
-};
+using Call = CallT<Work>;
 
 template <class T, int MODE>
 bool launch_lds(Call &c, const DecArgs &a, size_t lds) {
@@ -294,17 +241,15 @@ bool run_global(Call &c, const DecArgs &a, int sync_every, int *d_fail, uint32_t
 
 int fec_calc_llr(int device, int64_t n, int dtype, int M, double sigma2, const double *table, const int32_t *bitmap, const double *px,
                  const void *x, double *llr_out, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     int b = 0;
     while ((1 << b) < M) ++b;
     const size_t out_bytes = (size_t)n * b * sizeof(double);
     double *out = (double *)c.target(llr_out, w.out, out_bytes);
     if (!out) return c.rc;
-    const void *xd = c.input(x, w.in, (size_t)n * (dtype == mk::kC128 ? 16 : 8));
+    const void *xd = c.input(x, w.in, (size_t)n * mk::elem_size(dtype));
     if (!xd) return c.rc;
     // [table 2 M doubles | px M doubles | zero masks M | one masks M]
     const size_t tab_bytes = (size_t)M * (3 * sizeof(double) + 2 * sizeof(unsigned));
@@ -339,10 +284,8 @@ int fec_calc_llr(int device, int64_t n, int dtype, int M, double sigma2, const d
 
 int fec_graph_create(int device, int m, int n, int E, const int32_t *co, const int32_t *ev, const int32_t *vo, const int32_t *ve,
                      int max_dc, ssf_ldpc_graph **out, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.ok(hipSetDevice(device), "hipSetDevice")) return c.rc;
+    Call c(device, err, false);
+    if (c.rc) return c.rc;
     ssf_ldpc_graph *g = new ssf_ldpc_graph();
     g->device = device, g->m = m, g->n = n, g->E = E, g->max_dc = max_dc;
     const size_t total = (size_t)(m + 1) + (size_t)(n + 1) + 2 * (size_t)E;
@@ -365,20 +308,16 @@ int fec_graph_create(int device, int m, int n, int E, const int32_t *co, const i
 }
 
 int fec_graph_destroy(ssf_ldpc_graph *g, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (c.ok(hipSetDevice(g->device), "hipSetDevice")) c.ok(hipFree(g->d_all), "hipFree");
+    Call c(g->device, err, false);
+    if (!c.rc) c.ok(hipFree(g->d_all), "hipFree");
     delete g;
     return c.rc;
 }
 
 int fec_decode(int device, const ssf_ldpc_graph *g, const ssf_ldpc_params *p, const void *llr_in, void *llr_out, int8_t *bits_out,
                int8_t *fail_out, uint32_t *iter_out, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     const int ncw = p->numCodewords, n_ = p->n_;
     const size_t wsz = p->prec == kF64 ? 8 : 4, isz = p->in_dtype == kF64 ? 8 : 4;

@@ -4,19 +4,18 @@
 // workgroup, and the partials are added in a fixed order: no floating-point atomics, results repeat bit for bit.
 #include <hip/hip_runtime.h>
 
-#include <map>
-#include <mutex>
-#include <string>
 #include <vector>
 
+#include "block_reduce.h"
+#include "engine_host.h"
 #include "metrics_kernels.h"
-#include "ssf_internal.h"
 
 namespace ssf {
 namespace {
 using namespace mk;
+using namespace eng;
 
-constexpr int kBlock = 256, kWaves = kBlock / 64, kMaxBlocks = 512;
+constexpr int kBlock = br::kBlock, kMaxBlocks = 512;
 constexpr int kPwDepth = 16;              // frames of the pairwise recursion inside one chunk of 8192 (it needs 7)
 
 struct KArgs {
@@ -33,34 +32,12 @@ struct KArgs {
     long long nleaf;
 };
 
-// K running sums of this workgroup -> out[0 .. K)
-template <int K> __device__ void block_store(double (&acc)[K], double *out) {
-    __shared__ double sh[kWaves][K];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-        if (lane == 0) sh[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        const int k = threadIdx.x;
-        out[k] = ((sh[0][k] + sh[1][k]) + sh[2][k]) + sh[3][k];
-    }
-}
-
-// one wave: tot[mode * K + v] = sum over the nb partials of that mode, lane-strided then a fixed shuffle tree
+// one wave: tot[mode * K + v] = sum over the nb partials of that mode
 template <int K> __device__ void sum_partials(const double *part, int nb, int nModes, double *tot) {
-    const int lane = threadIdx.x;
     for (int q = 0; q < nModes * K; ++q) {
         const int k = q / K, v = q - k * K;
-        double a = 0.0;
-        for (int b = lane; b < nb; b += 64) a += part[((long long)k * nb + b) * K + v];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_down(a, o, 64);
-        if (lane == 0) tot[q] = a;
+        const double a = br::wave_sum_partials(part + (long long)k * nb * K + v, nb, K);
+        if (threadIdx.x == 0) tot[q] = a;
     }
     __syncthreads();
 }
@@ -79,7 +56,7 @@ __global__ __launch_bounds__(kBlock) void k_stats(KArgs a) {
         if (a.has_tx) load(a.dtype, a.tx, off, tr, ti);
         stats_body(acc, a.rotate != 0, a.has_tx != 0, rr, ri, tr, ti);
     }
-    block_store<kStatN>(acc, a.part + ((long long)k * gridDim.x + blockIdx.x) * kStatN);
+    br::block_sum_store<kStatN>(acc, a.part + ((long long)k * gridDim.x + blockIdx.x) * kStatN);
 }
 
 __global__ __launch_bounds__(64) void k_stats_fin(KArgs a) {
@@ -107,7 +84,7 @@ __global__ __launch_bounds__(kBlock) void k_decide(KArgs a) {
         load(a.dtype, a.tx, off, tr, ti);
         decide_body(acc, s, lds, a.M, a.sqrtEs, a.want, rr, ri, tr, ti);
     }
-    block_store<kDecN>(acc, a.part + ((long long)k * gridDim.x + blockIdx.x) * kDecN);
+    br::block_sum_store<kDecN>(acc, a.part + ((long long)k * gridDim.x + blockIdx.x) * kDecN);
 }
 
 __global__ __launch_bounds__(64) void k_decide_fin(KArgs a) {
@@ -137,7 +114,7 @@ __global__ __launch_bounds__(kBlock) void k_soft(KArgs a) {
         load(a.dtype, a.tx, off, tr, ti);
         SoftDispatch<1>::run(a.bits, acc, s, raw, cn, px, l2, M, a.sqrtEs, rr, ri, tr, ti);
     }
-    block_store<kSoftN>(acc, a.part + ((long long)k * gridDim.x + blockIdx.x) * kSoftN);
+    br::block_sum_store<kSoftN>(acc, a.part + ((long long)k * gridDim.x + blockIdx.x) * kSoftN);
 }
 
 __global__ __launch_bounds__(64) void k_soft_fin(KArgs a) {
@@ -160,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void k_blind(KArgs a) {
         load(a.dtype, a.rx, (a.n0 + i) * a.sn + k * a.sm, rr, ri);
         a.idx[(long long)k * a.n + i] = blind_body(acc, jrx, lds, a.M, rr, ri);
     }
-    block_store<1>(acc, a.part + ((long long)k * gridDim.x + blockIdx.x));
+    br::block_sum_store<1>(acc, a.part + ((long long)k * gridDim.x + blockIdx.x));
 }
 
 __global__ __launch_bounds__(kBlock) void k_pw_leaf(KArgs a) {
@@ -216,66 +193,20 @@ __global__ __launch_bounds__(kBlock) void k_scale(KArgs a, void *y) {
 }
 
 // ---- host side
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr, cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
+struct Work : WorkBase {
+    Buf tables, part, scal, res, idx, leaf_sum, in_rx, in_tx, out;
+    PwLeaves leaves;
+    std::vector<double> host_tab;             // sources of asynchronous uploads: they outlive the call
+    std::vector<float> host_w32;
 };
-struct Work {
-    hipStream_t st = nullptr;
-    Buf tables, part, scal, res, idx, leaf_start, leaf_sum, in_rx, in_tx, out;
-};
-std::mutex g_mu;
-std::map<int, Work> g_work;
-
-size_t elem_size(int dtype) { return dtype == kC128 ? 16 : (dtype == kF32 ? 4 : 8); }
-
-struct Call {
-    Work *w = nullptr;
-    std::string *err;
-    int rc = SSF_OK;
-    bool ok(hipError_t e, const char *what) {
-        if (e == hipSuccess) return true;
-        rc = e == hipErrorOutOfMemory ? SSF_ERR_OOM : SSF_ERR_HIP;
-        *err = std::string(what) + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return false;
-    }
-    bool begin(int device) {
-        if (!ok(hipSetDevice(device), "hipSetDevice")) return false;
-        w = &g_work[device];
-        if (!w->st && !ok(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking), "hipStreamCreate")) return false;
-        return true;
-    }
-    // device view of an array argument: a device pointer as it is, host memory through a staging buffer
-    const void *input(Buf &b, const void *p, size_t bytes) {
-        if (on_device(p)) return p;
-        if (!ok(b.need(bytes), "hipMalloc")) return nullptr;
-        if (!ok(hipMemcpyAsync(b.p, p, bytes, hipMemcpyHostToDevice, w->st), "hipMemcpy")) return nullptr;
-        return b.p;
-    }
-};
-
-int grid_blocks(long long n) {
-    const long long nb = (n + kBlock - 1) / kBlock;
-    return (int)(nb < kMaxBlocks ? nb : kMaxBlocks);
-}
+using Call = CallT<Work>;
 
 }  // namespace
 
 int metrics_run(int device, const ssf_metrics_params *p, const void *rx, const void *tx, const double *const_raw,
                 const double *const_norm, const double *px, const float *evm_w32, ssf_metrics_result *out, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     const int M = p->M, nModes = p->nModes;
     const bool blind = (p->want & kWantEvmBlind) != 0;
@@ -286,12 +217,14 @@ int metrics_run(int device, const ssf_metrics_params *p, const void *rx, const v
     a.n0 = p->discard, a.n = p->n - 2 * p->discard;
     a.sn = p->transposed ? 1 : nModes, a.sm = p->transposed ? p->n : 1;
     a.nModes = nModes, a.M = M, a.bits = bits, a.dtype = p->dtype, a.rotate = p->rotate, a.has_tx = tx != nullptr, a.want = p->want;
-    a.nb = grid_blocks(a.n);
+    a.nb = grid_blocks(a.n, kBlock, kMaxBlocks);
     a.sqrtEs = std::sqrt(p->Es), a.H = p->H;
 
     // tables: raw (2M) | normalised (2M) | px (M) | log2 px (M) doubles, then M float weights
-    std::vector<double> tab(6 * (size_t)M, 0.0);
-    std::vector<float> w32(M, 0.f);
+    std::vector<double> &tab = w.host_tab;
+    std::vector<float> &w32 = w.host_w32;
+    tab.assign(6 * (size_t)M, 0.0);
+    w32.assign(M, 0.f);
     for (int m = 0; m < 2 * M; ++m) tab[m] = const_raw ? const_raw[m] : 0.0, tab[2 * M + m] = const_norm[m];
     for (int m = 0; m < M; ++m) {
         tab[4 * M + m] = px ? px[m] : 1.0 / M;
@@ -299,13 +232,13 @@ int metrics_run(int device, const ssf_metrics_params *p, const void *rx, const v
         if (evm_w32) w32[m] = evm_w32[m];
     }
     const size_t tab_bytes = tab.size() * sizeof(double);
-    if (!c.ok(w.tables.need(tab_bytes + M * sizeof(float)), "hipMalloc")) return c.rc;
-    if (!c.ok(w.part.need((size_t)nModes * kMaxBlocks * kDecN * sizeof(double)), "hipMalloc")) return c.rc;
-    if (!c.ok(w.scal.need((size_t)kMaxModes * kScalN * sizeof(double)), "hipMalloc")) return c.rc;
-    if (!c.ok(w.res.need((size_t)kMaxModes * kResN * sizeof(double)), "hipMalloc")) return c.rc;
+    if (!c.need(w.tables, tab_bytes + M * sizeof(float))) return c.rc;
+    if (!c.need(w.part, (size_t)nModes * kMaxBlocks * kDecN * sizeof(double))) return c.rc;
+    if (!c.need(w.scal, (size_t)kMaxModes * kScalN * sizeof(double))) return c.rc;
+    if (!c.need(w.res, (size_t)kMaxModes * kResN * sizeof(double))) return c.rc;
     const size_t in_bytes = (size_t)p->n * nModes * elem_size(p->dtype);
-    if (!(a.rx = c.input(w.in_rx, rx, in_bytes))) return c.rc;
-    if (tx && !(a.tx = c.input(w.in_tx, tx, in_bytes))) return c.rc;
+    if (!(a.rx = c.input(rx, w.in_rx, in_bytes))) return c.rc;
+    if (tx && !(a.tx = c.input(tx, w.in_tx, in_bytes))) return c.rc;
     if (!c.ok(hipMemcpyAsync(w.tables.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
     if (!c.ok(hipMemcpyAsync((char *)w.tables.p + tab_bytes, w32.data(), M * sizeof(float), hipMemcpyHostToDevice, w.st), "hipMemcpy"))
         return c.rc;
@@ -314,18 +247,11 @@ int metrics_run(int device, const ssf_metrics_params *p, const void *rx, const v
     a.part = (double *)w.part.p, a.scal = (double *)w.scal.p, a.res = (double *)w.res.p;
     if (!c.ok(hipMemsetAsync(w.res.p, 0, (size_t)kMaxModes * kResN * sizeof(double), w.st), "hipMemset")) return c.rc;
 
-    std::vector<long long> starts;
     if (blind) {
-        a.nleaf = pw_leaves(a.n, nullptr);
-        starts.resize(a.nleaf + 1);
-        pw_leaves(a.n, starts.data());
-        starts[a.nleaf] = a.n;
-        if (!c.ok(w.idx.need((size_t)a.n * nModes * sizeof(int32_t)), "hipMalloc")) return c.rc;
-        if (!c.ok(w.leaf_start.need(starts.size() * sizeof(long long)), "hipMalloc")) return c.rc;
-        if (!c.ok(w.leaf_sum.need((size_t)a.nleaf * nModes * sizeof(float)), "hipMalloc")) return c.rc;
-        if (!c.ok(hipMemcpyAsync(w.leaf_start.p, starts.data(), starts.size() * sizeof(long long), hipMemcpyHostToDevice, w.st), "hipMemcpy"))
-            return c.rc;
-        a.idx = (int32_t *)w.idx.p, a.leaf_start = (const long long *)w.leaf_start.p, a.leaf_sum = (float *)w.leaf_sum.p;
+        if (!pairwise_leaves(c, w.leaves, a.n, a.nleaf, a.leaf_start)) return c.rc;
+        if (!c.need(w.idx, (size_t)a.n * nModes * sizeof(int32_t))) return c.rc;
+        if (!c.need(w.leaf_sum, (size_t)a.nleaf * nModes * sizeof(float))) return c.rc;
+        a.idx = (int32_t *)w.idx.p, a.leaf_sum = (float *)w.leaf_sum.p;
     }
 
     const dim3 grid(a.nb, nModes), block(kBlock);
@@ -343,10 +269,10 @@ int metrics_run(int device, const ssf_metrics_params *p, const void *rx, const v
             k_soft_fin<<<1, 64, 0, w.st>>>(a);
         }
     }
-    if (!c.ok(hipGetLastError(), "kernel launch")) return c.rc;
+    if (!c.launched()) return c.rc;
     std::vector<double> res((size_t)nModes * kResN);
-    if (!c.ok(hipMemcpyAsync(res.data(), w.res.p, res.size() * sizeof(double), hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return c.rc;
-    if (!c.ok(hipStreamSynchronize(w.st), "hipStreamSynchronize")) return c.rc;
+    if (!c.deliver(res.data(), w.res.p, res.size() * sizeof(double))) return c.rc;
+    if (!c.sync()) return c.rc;
     for (int k = 0; k < nModes; ++k) {
         const double *r = res.data() + (size_t)k * kResN;
         ssf_metrics_result &o = out[k];
@@ -359,71 +285,63 @@ int metrics_run(int device, const ssf_metrics_params *p, const void *rx, const v
 // power statistics of `count` values taken as one column: scal[6] = sqrt(mean |x|^2), scal[9] = sum |x|^2
 static bool flat_stats(Call &c, KArgs &a, int64_t count, int dtype, const void *x) {
     Work &w = *c.w;
-    if (!c.ok(w.part.need((size_t)kMaxBlocks * kDecN * sizeof(double)), "hipMalloc")) return false;
-    if (!c.ok(w.scal.need((size_t)kMaxModes * kScalN * sizeof(double)), "hipMalloc")) return false;
-    if (!(a.rx = c.input(w.in_rx, x, (size_t)count * elem_size(dtype)))) return false;
-    a.n0 = 0, a.n = count, a.sn = 1, a.sm = 0, a.nModes = 1, a.dtype = dtype, a.nb = grid_blocks(count);
+    if (!c.need(w.part, (size_t)kMaxBlocks * kDecN * sizeof(double))) return false;
+    if (!c.need(w.scal, (size_t)kMaxModes * kScalN * sizeof(double))) return false;
+    if (!(a.rx = c.input(x, w.in_rx, (size_t)count * elem_size(dtype)))) return false;
+    a.n0 = 0, a.n = count, a.sn = 1, a.sm = 0, a.nModes = 1, a.dtype = dtype, a.nb = grid_blocks(count, kBlock, kMaxBlocks);
     a.part = (double *)w.part.p, a.scal = (double *)w.scal.p;
     k_stats<<<dim3(a.nb, 1), kBlock, 0, w.st>>>(a);
     k_stats_fin<<<1, 64, 0, w.st>>>(a);
-    return c.ok(hipGetLastError(), "kernel launch");
+    return c.launched();
 }
 
 int metrics_pnorm(int device, int64_t count, int dtype, const void *x, void *y, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     KArgs a{};
     const size_t out_bytes = (size_t)count * ((dtype == kC128 || dtype == kC64) ? 16 : 8);
-    const bool y_dev = on_device(y);
-    if (!y_dev && !c.ok(w.out.need(out_bytes), "hipMalloc")) return c.rc;
+    void *yd = c.target(y, w.out, out_bytes);
+    if (!yd) return c.rc;
     if (!flat_stats(c, a, count, dtype, x)) return c.rc;
-    void *yd = y_dev ? y : w.out.p;
     k_scale<<<a.nb, kBlock, 0, w.st>>>(a, yd);
-    if (!c.ok(hipGetLastError(), "kernel launch")) return c.rc;
-    if (!y_dev && !c.ok(hipMemcpyAsync(y, yd, out_bytes, hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return c.rc;
-    if (!c.ok(hipStreamSynchronize(w.st), "hipStreamSynchronize")) return c.rc;
+    if (!c.launched()) return c.rc;
+    if (!c.deliver(y, yd, out_bytes)) return c.rc;
+    if (!c.sync()) return c.rc;
     return SSF_OK;
 }
 
 int metrics_power(int device, int64_t count, int64_t rows, int dtype, const void *x, double *out, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     KArgs a{};
     if (!flat_stats(c, a, count, dtype, x)) return c.rc;
     double total = 0.0;
-    if (!c.ok(hipMemcpyAsync(&total, a.scal + 9, sizeof(double), hipMemcpyDeviceToHost, c.w->st), "hipMemcpy")) return c.rc;
-    if (!c.ok(hipStreamSynchronize(c.w->st), "hipStreamSynchronize")) return c.rc;
+    if (!c.deliver(&total, a.scal + 9, sizeof(double))) return c.rc;
+    if (!c.sync()) return c.rc;
     *out = total / (double)rows;                                            // sum over the columns of mean |x|^2
     return SSF_OK;
 }
 
 int metrics_demod(int device, int64_t count, int dtype, int M, const double *const_raw, const void *symb, int32_t *bits_out,
                   std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     KArgs a{};
     int bits = 0;
     while ((1 << bits) < M) ++bits;
     const size_t out_bytes = (size_t)count * bits * sizeof(int32_t);
-    const bool o_dev = on_device(bits_out);
-    if (!c.ok(w.tables.need(2 * (size_t)M * sizeof(double)), "hipMalloc")) return c.rc;
-    if (!o_dev && !c.ok(w.out.need(out_bytes), "hipMalloc")) return c.rc;
-    if (!(a.rx = c.input(w.in_rx, symb, (size_t)count * elem_size(dtype)))) return c.rc;
+    if (!c.need(w.tables, 2 * (size_t)M * sizeof(double))) return c.rc;
+    int32_t *od = (int32_t *)c.target(bits_out, w.out, out_bytes);
+    if (!od) return c.rc;
+    if (!(a.rx = c.input(symb, w.in_rx, (size_t)count * elem_size(dtype)))) return c.rc;
     if (!c.ok(hipMemcpyAsync(w.tables.p, const_raw, 2 * (size_t)M * sizeof(double), hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
     a.n = count, a.M = M, a.bits = bits, a.dtype = dtype, a.raw = (const double *)w.tables.p;
-    int32_t *od = o_dev ? bits_out : (int32_t *)w.out.p;
-    k_demod<<<grid_blocks(count), kBlock, 2 * M * sizeof(double), w.st>>>(a, od);
-    if (!c.ok(hipGetLastError(), "kernel launch")) return c.rc;
-    if (!o_dev && !c.ok(hipMemcpyAsync(bits_out, od, out_bytes, hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return c.rc;
-    if (!c.ok(hipStreamSynchronize(w.st), "hipStreamSynchronize")) return c.rc;
+    k_demod<<<grid_blocks(count, kBlock, kMaxBlocks), kBlock, 2 * M * sizeof(double), w.st>>>(a, od);
+    if (!c.launched()) return c.rc;
+    if (!c.deliver(bits_out, od, out_bytes)) return c.rc;
+    if (!c.sync()) return c.rc;
     return SSF_OK;
 }
 

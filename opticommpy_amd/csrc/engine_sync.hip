@@ -10,22 +10,18 @@
 //   gather    out[i, k] = f(tx[(i + delay[k]) mod n_tx, swap[k]]); swap, rot, conj, delay are read from device memory
 // No host decision between the launches; the record is copied once at the end.  No floating-point atomics.
 #include <hip/hip_runtime.h>
-#include <rocfft/rocfft.h>
 
-#include <map>
-#include <mutex>
-#include <string>
-#include <tuple>
-#include <vector>
-
-#include "ssf_internal.h"
+#include "block_reduce.h"
+#include "engine_host.h"
 #include "sync_kernels.h"
 
 namespace ssf {
 namespace {
 using namespace sk;
+using namespace eng;
 
-constexpr int kWaves = kBlock / 64;
+static_assert(kBlock == br::kBlock, "block_reduce.h is written for this workgroup");
+constexpr int kWaves = br::kWaves;
 constexpr int kPwDepth = 16;                  // frames of the pairwise recursion inside one chunk of 8192 (it needs 7)
 
 struct SyncArgs {
@@ -45,20 +41,8 @@ struct SyncArgs {
     void *out;
 };
 
-// one running sum per workgroup -> out[0], fixed order
-__device__ void block_sum_store(double v, double *out, double *shw) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    __syncthreads();
-    if (lane == 0) shw[wave] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = ((shw[0] + shw[1]) + shw[2]) + shw[3];
-}
-
 // one lane per row: consecutive lanes read consecutive rows of nModes elements each
 __global__ __launch_bounds__(kBlock) void k_prepare(SyncArgs a) {
-    __shared__ double shw[kWaves];
     double acc[kMaxModes];
 #pragma unroll
     for (int m = 0; m < kMaxModes; ++m) acc[m] = 0.0;
@@ -86,7 +70,7 @@ __global__ __launch_bounds__(kBlock) void k_prepare(SyncArgs a) {
     }
     if (a.mode != kAmp) return;
     for (int m = 0; m < a.nModes; ++m)
-        block_sum_store(acc[m], a.part + ((long long)a.side * kMaxBlocks + blockIdx.x) * kMaxModes + m, shw);
+        br::block_sum_store(acc[m], a.part + ((long long)a.side * kMaxBlocks + blockIdx.x) * kMaxModes + m);
 }
 
 __global__ __launch_bounds__(kBlock) void k_pw_leaf(SyncArgs a) {
@@ -207,134 +191,24 @@ __global__ __launch_bounds__(kBlock) void k_widen(const CplxF *x, Cplx *y, long 
 }
 
 // ---- host side
-struct Buf {
-    void *p = nullptr;
-    size_t cap = 0;
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr, cap = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
+struct Work : WorkBase {
+    Buf in_x, in_y, wide, dec, F, G, part, mean, leaf_sum, cand, peak, rec, out;
+    FftPlans plans;
+    PwLeaves leaves;
 };
-struct FftPlan {
-    rocfft_plan plan = nullptr;
-    rocfft_execution_info info = nullptr;
-    void *work = nullptr;
-};
-struct Work {
-    hipStream_t st = nullptr;
-    Buf in_x, in_y, wide, dec, F, G, part, mean, leaf_start, leaf_sum, cand, peak, rec, out;
-    std::map<std::tuple<long long, int, int>, FftPlan> plans;      // (L, batch, inverse)
-    std::vector<long long> host_leaves;                              // source of an asynchronous upload: it outlives the call
-    long long leaves_of = -1;
-};
-std::mutex g_mu;
-std::map<int, Work> g_work;
-std::once_flag g_fft_once;
-
-size_t elem_size(int dtype) { return dtype == mk::kC128 ? 16 : dtype == mk::kC64 || dtype == mk::kF64 ? 8 : 4; }
-
-struct Call {
-    Work *w = nullptr;
-    std::string *err;
-    int rc = SSF_OK;
-    bool ok(hipError_t e, const char *what) {
-        if (e == hipSuccess) return true;
-        rc = e == hipErrorOutOfMemory ? SSF_ERR_OOM : SSF_ERR_HIP;
-        *err = std::string(what) + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return false;
-    }
-    bool fft_fail(const char *what) {
-        rc = SSF_ERR_FFT, *err = what;
-        return false;
-    }
-    bool begin(int device) {
-        if (!ok(hipSetDevice(device), "hipSetDevice")) return false;
-        w = &g_work[device];
-        if (!w->st && !ok(hipStreamCreateWithFlags(&w->st, hipStreamNonBlocking), "hipStreamCreate")) return false;
-        return true;
-    }
-    bool need(Buf &b, size_t bytes) { return ok(b.need(bytes), "hipMalloc"); }
-    const void *input(const void *p, Buf &stage, size_t bytes) {
-        if (on_device(p)) return p;
-        if (!need(stage, bytes)) return nullptr;
-        if (!ok(hipMemcpyAsync(stage.p, p, bytes, hipMemcpyHostToDevice, w->st), "hipMemcpy")) return nullptr;
-        return stage.p;
-    }
-    bool launched() { return ok(hipGetLastError(), "kernel launch"); }
-    bool sync() { return ok(hipStreamSynchronize(w->st), "hipStreamSynchronize"); }
-};
-
-int grid_blocks(long long count) {
-    const long long nb = (count + kBlock - 1) / kBlock;
-    return (int)(nb < 1 ? 1 : nb < kMaxBlocks ? nb : kMaxBlocks);
-}
-
-bool get_plan(Call &c, long long L, int batch, bool inverse, FftPlan **out) {
-    Work &w = *c.w;
-    std::call_once(g_fft_once, [] { rocfft_setup(); });
-    FftPlan &p = w.plans[std::make_tuple(L, batch, (int)inverse)];
-    if (!p.plan) {
-        const size_t len = (size_t)L;
-        if (rocfft_plan_create(&p.plan, rocfft_placement_inplace, inverse ? rocfft_transform_type_complex_inverse : rocfft_transform_type_complex_forward,
-                               rocfft_precision_double, 1, &len, (size_t)batch, nullptr) != rocfft_status_success) {
-            p.plan = nullptr;
-            return c.fft_fail("rocfft_plan_create failed");
-        }
-        size_t ws = 0;
-        rocfft_plan_get_work_buffer_size(p.plan, &ws);
-        if (rocfft_execution_info_create(&p.info) != rocfft_status_success) return c.fft_fail("rocfft_execution_info_create failed");
-        if (ws) {
-            if (!c.ok(hipMalloc(&p.work, ws), "hipMalloc")) return false;
-            rocfft_execution_info_set_work_buffer(p.info, p.work, ws);
-        }
-        rocfft_execution_info_set_stream(p.info, w.st);
-    }
-    *out = &p;
-    return true;
-}
-bool transform(Call &c, void *buf, long long L, int batch, bool inverse) {
-    FftPlan *plan = nullptr;
-    if (!get_plan(c, L, batch, inverse, &plan)) return false;
-    void *io[1] = {buf};
-    if (rocfft_execute(plan->plan, io, nullptr, plan->info) != rocfft_status_success) return c.fft_fail("rocfft_execute failed");
-    return true;
-}
-
-// the leaves of numpy's pairwise sum over n elements, on the device (kept while n stays the same)
-bool pairwise_leaves(Call &c, long long n, SyncArgs &a) {
-    Work &w = *c.w;
-    a.nleaf = mk::pw_leaves(n, nullptr);
-    if (!c.need(w.leaf_sum, (size_t)kMaxModes * a.nleaf * sizeof(float))) return false;
-    a.leaf_sum = (float *)w.leaf_sum.p;
-    if (w.leaves_of != n) {
-        if (!c.sync()) return false;                                // an earlier upload may still read host_leaves
-        w.host_leaves.assign(a.nleaf + 1, n);
-        mk::pw_leaves(n, w.host_leaves.data());
-        w.leaves_of = -1;
-        if (!c.need(w.leaf_start, w.host_leaves.size() * sizeof(long long))) return false;
-        if (!c.ok(hipMemcpyAsync(w.leaf_start.p, w.host_leaves.data(), w.host_leaves.size() * sizeof(long long), hipMemcpyHostToDevice, w.st),
-                  "hipMemcpy"))
-            return false;
-        w.leaves_of = n;
-    }
-    a.leaf_start = (const long long *)w.leaf_start.p;
-    return true;
-}
+using Call = CallT<Work>;
 
 // one side into the transform buffers, centred in 'amp'
 bool prepare(Call &c, SyncArgs a, int side, const void *x, int dtype, bool f32, long long n, long long off) {
     Work &w = *c.w;
     a.side = side, a.x = x, a.dtype = dtype, a.f32 = f32, a.n = n, a.off = off;
-    a.nb = grid_blocks(n);
+    a.nb = grid_blocks(n, kBlock, kMaxBlocks, 1);
     k_prepare<<<a.nb, kBlock, 0, w.st>>>(a);
     if (a.mode == kAmp) {
         if (f32) {
-            if (!pairwise_leaves(c, n, a)) return false;
+            if (!pairwise_leaves(c, w.leaves, n, a.nleaf, a.leaf_start)) return false;
+            if (!c.need(w.leaf_sum, (size_t)kMaxModes * a.nleaf * sizeof(float))) return false;
+            a.leaf_sum = (float *)w.leaf_sum.p;
             k_pw_leaf<<<dim3((unsigned)((a.nleaf + kBlock - 1) / kBlock), a.nModes), kBlock, 0, w.st>>>(a);
         }
         k_means<<<1, 64, 0, w.st>>>(a);
@@ -347,10 +221,10 @@ bool prepare(Call &c, SyncArgs a, int side, const void *x, int dtype, bool f32, 
 bool correlate(Call &c, SyncArgs a, int round, int nslots, int peak_base) {
     Work &w = *c.w;
     a.round = round, a.nslots = nslots, a.peak_base = peak_base;
-    k_product<<<dim3(grid_blocks(a.L), nslots), kBlock, 0, w.st>>>(a);
+    k_product<<<dim3(grid_blocks(a.L, kBlock, kMaxBlocks, 1), nslots), kBlock, 0, w.st>>>(a);
     if (!c.launched()) return false;
     if (!transform(c, a.G, a.L, nslots, true)) return false;
-    a.nb = grid_blocks(a.lags);
+    a.nb = grid_blocks(a.lags, kBlock, kMaxBlocks, 1);
     k_peaks<<<dim3(a.nb, nslots), kBlock, 0, w.st>>>(a);
     k_peaks_fin<<<2 * nslots, kBlock, 0, w.st>>>(a);
     k_decide<<<1, 64, 0, w.st>>>(a);
@@ -399,19 +273,13 @@ bool fetch_record(Call &c, Record &r, int cols, long long lags) {
 }  // namespace
 
 int sync_run(int device, const ssf_sync_params *p, const void *rx, const void *tx, void *out, ssf_sync_result *res, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     const int nModes = p->nModes;
-    const size_t tx_bytes = (size_t)p->n_tx * nModes * elem_size(p->tx_dtype), rx_count = (size_t)p->n_rx * nModes;
-    const bool out_dev = on_device(out);
-    void *o = out;
-    if (!out_dev) {
-        if (!c.need(w.out, tx_bytes)) return c.rc;
-        o = w.out.p;
-    }
+    const size_t tx_bytes = (size_t)p->n_tx * nModes * mk::elem_size(p->tx_dtype), rx_count = (size_t)p->n_rx * nModes;
+    void *o = c.target(out, w.out, tx_bytes);
+    if (!o) return c.rc;
     const void *txd = c.input(tx, w.in_x, tx_bytes);
     if (!txd) return c.rc;
     const void *rxd = nullptr;
@@ -423,7 +291,7 @@ int sync_run(int device, const ssf_sync_params *p, const void *rx, const void *t
         if (rx_dtype == mk::kC64) {
             const void *r32 = c.input(rx, w.in_y, rx_count * sizeof(CplxF));
             if (!r32 || !c.need(w.wide, rx_count * sizeof(Cplx))) return c.rc;
-            k_widen<<<grid_blocks((long long)rx_count), kBlock, 0, w.st>>>((const CplxF *)r32, (Cplx *)w.wide.p, (long long)rx_count);
+            k_widen<<<grid_blocks((long long)rx_count, kBlock, kMaxBlocks, 1), kBlock, 0, w.st>>>((const CplxF *)r32, (Cplx *)w.wide.p, (long long)rx_count);
             if (!c.launched() || !c.sync()) return c.rc;
             in = w.wide.p;
         }
@@ -433,17 +301,17 @@ int sync_run(int device, const ssf_sync_params *p, const void *rx, const void *t
         if (!c.ok(hipSetDevice(device), "hipSetDevice")) return c.rc;
         rxd = w.dec.p, rx_dtype = mk::kC128;
     } else {
-        rxd = c.input(rx, w.in_y, rx_count * elem_size(rx_dtype));
+        rxd = c.input(rx, w.in_y, rx_count * mk::elem_size(rx_dtype));
         if (!rxd) return c.rc;
     }
     if (!run(c, p->mode, nModes, txd, p->tx_dtype, p->tx_dtype == mk::kC64, p->n_tx, rxd, rx_dtype, p->rx_dtype == mk::kC64, n_rx)) return c.rc;
     SyncArgs g{};
     g.x = txd, g.out = o, g.n = p->n_tx, g.nModes = nModes, g.rec = (Record *)w.rec.p;
-    const int nb = grid_blocks(p->n_tx * nModes);
+    const int nb = grid_blocks(p->n_tx * nModes, kBlock, kMaxBlocks, 1);
     if (p->tx_dtype == mk::kC64) k_gather<CplxF><<<nb, kBlock, 0, w.st>>>(g);
     else k_gather<Cplx><<<nb, kBlock, 0, w.st>>>(g);
     if (!c.launched()) return c.rc;
-    if (!out_dev && !c.ok(hipMemcpyAsync(out, o, tx_bytes, hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return c.rc;
+    if (!c.deliver(out, o, tx_bytes)) return c.rc;
     Record r;
     if (!fetch_record(c, r, nModes, p->n_tx + n_rx - 1)) return c.rc;
     if (res) {
@@ -456,13 +324,11 @@ int sync_run(int device, const ssf_sync_params *p, const void *rx, const void *t
 
 int sync_finddelay(int device, int64_t nx, int64_t ny, int x_dtype, int y_dtype, const void *x, const void *y, int64_t *delay_out,
                    std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
-    const void *xd = c.input(x, w.in_x, (size_t)nx * elem_size(x_dtype));
-    const void *yd = xd ? c.input(y, w.in_y, (size_t)ny * elem_size(y_dtype)) : nullptr;
+    const void *xd = c.input(x, w.in_x, (size_t)nx * mk::elem_size(x_dtype));
+    const void *yd = xd ? c.input(y, w.in_y, (size_t)ny * mk::elem_size(y_dtype)) : nullptr;
     if (!xd || !yd) return c.rc;
     if (!run(c, kDelay, 1, xd, x_dtype, false, nx, yd, y_dtype, false, ny)) return c.rc;
     Record r;
@@ -474,10 +340,8 @@ int sync_finddelay(int device, int64_t nx, int64_t ny, int x_dtype, int y_dtype,
 // the call's transforms alone, on the engine's own buffers and plans: seconds per round of (forward x nseq, inverse x nslots,
 // inverse x nslots2), from device events around `reps` rounds (tools/bench_sync.py: the floor the kernels add to)
 int sync_transform_time(int device, int64_t L, int nseq, int nslots, int nslots2, int reps, double *seconds_out, std::string *err) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Call c;
-    c.err = err;
-    if (!c.begin(device)) return c.rc;
+    Call c(device, err);
+    if (c.rc) return c.rc;
     Work &w = *c.w;
     const size_t seq_bytes = (size_t)L * sizeof(Cplx);
     if (!c.need(w.F, nseq * seq_bytes) || !c.need(w.G, nslots * seq_bytes)) return c.rc;

@@ -7,6 +7,7 @@
 // Arithmetic is double whatever the input type; single-precision inputs are widened on load.
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 #if defined(__HIPCC__)
@@ -32,6 +33,9 @@ struct alignas(16) Cplx {
 struct alignas(8) CplxF {
     float re, im;
 };
+
+// bytes of one element of the given type
+MK_HD size_t elem_size(int dtype) { return dtype == kC128 ? 16 : dtype == kF32 ? 4 : 8; }
 
 // element `off` of an array of the given type (16 B per lane for complex128)
 MK_HD void load(int dtype, const void *p, long long off, double &re, double &im) {
