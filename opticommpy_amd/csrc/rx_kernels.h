@@ -667,8 +667,8 @@ template <int LG, int C, int MODE, class Ctx> SSF_HD void chain_ols_body(Ctx &ct
                 t2 += red[3 * t + 2];
             }
             // the class of this chain: the one its threads stored under -- or, for a chain that stored nothing (beyond the signal's
-            // end, an idle group), any class with zeros; every (group, class) slot is written exactly once because the SpS chains of a
-            // column cover the SpS phases
+            // end, an idle group), any class with zeros; every (group, class) slot of the group's C columns is written exactly once
+            // because the SpS chains of a column cover the SpS phases (the other columns' slots, C = 1 of two: zeroed by the host)
             const long long job = (long long)ctx.bid * gpw + g;
             const int ncg = a.o.nrows / C;
             const long long jb = ncg == 1 ? job : job / ncg;

@@ -534,6 +534,9 @@ template <class Backend> struct RxCore {
             owned.push_back(dpart);
             ca.part = dpart;
             ca.SpS = SpSin;
+            // a block group writes the slots of its own C columns only: where it takes one of the two (8192-point blocks) the
+            // other column's slots of its partial must read as zero
+            if (lo.C < nm) be.memset(dpart, 0, sizeof(double) * 3 * (size_t)nparts * nclass);
             be.launch_chain_ols(ca, CH_STATS);
             ChainFinishArgs fa{dpart, ddelay, nparts, nclass, nm, SpSin, (double)(N / SpSin)};
             be.launch_chain_finish(fa);

@@ -202,7 +202,13 @@ void run_grid(int grid, int block, size_t lds, const std::function<void(EmuCtx &
 
 struct EmuBackend {
     long launches = 0;
-    void *alloc(size_t n) { return calloc(n ? n : 1, 1); }
+    // (fresh device memory holds anything: every byte 0xFF -- NaN as a double, -1 as an int -- so that a kernel that reads what no
+    //  kernel wrote cannot pass here by finding zeros)
+    void *alloc(size_t n) {
+        void *p = malloc(n ? n : 1);
+        if (p) ::memset(p, 0xFF, n ? n : 1);
+        return p;
+    }
     void free(void *p) { ::free(p); }
     void h2d(void *d, const void *h, size_t n) { memcpy(d, h, n); }
     void d2h(void *h, const void *d, size_t n) { memcpy(h, d, n); }
@@ -564,7 +570,7 @@ int emu_overlap_save(int64_t sigLen, int nrows, int lg, int K, const void *Hfft,
 }
 
 static long g_rx_launches = 0;
-long emu_rx_launches() { return g_rx_launches; }                   // kernel launches of the last emu_rx_run
+long emu_rx_launches() { return g_rx_launches; }                   // kernel launches of the last emu_rx_run / emu_rx_chain / emu_fir_long
 int emu_rx_run(int mode, int64_t N, int nmodes, const ssf_rx_params *p, const void *in0, const void *lo, const double *un, void *out) {
     EmuBackend be;
     ssf::rx::RxCore<EmuBackend> core(be);
@@ -591,7 +597,9 @@ int emu_fir(int64_t sigLen, int ncols, int ntaps, const void *taps, const void *
 int emu_fir_long(int64_t inLen, int64_t outLen, int ncols, int64_t ntaps, const void *taps, int64_t shift, const void *in, void *out) {
     EmuBackend be;
     ssf::rx::RxCore<EmuBackend> core(be);
-    return core.fir_long(inLen, outLen, ncols, ntaps, taps, shift, in, out);
+    const int rc = core.fir_long(inLen, outLen, ncols, ntaps, taps, shift, in, out);
+    g_rx_launches = be.launches;                                   // (one per segment of the impulse response that meets the signal)
+    return rc;
 }
 int emu_nlin_phase_rot(int64_t n, double gamma, const void *Ex, const void *Ey, const double *Pch, double *phi) {
     EmuBackend be;
