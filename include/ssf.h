@@ -709,6 +709,49 @@ typedef struct {
 int  ssf_ldpc_decode(int device, const ssf_ldpc_graph *graph, const ssf_ldpc_params *params, const void *llr_in, void *llr_out,
                      int8_t *bits_out, int8_t *fail_out, uint32_t *iter_out);
 
+/* ---- the transmit side of the coded link: LDPC encoding and Gray mapping (optic/comm/fec.py:153-344 encodeLDPC, encodeDVBS2,
+ * encoder, 1019-1072 encodeTriang; optic/comm/modulation.py:334-366 modulateGray).  Arithmetic is GF(2) and a table lookup: the
+ * results are the reference's, bit for bit, and repeat.
+ *
+ * An encoder is one code's matrices on one device, uploaded once and used by any number of encodes.  Two forms:
+ *   SSF_ENC_DENSE    up to two parity blocks of m1 and m2 rows (m2 may be 0), each row (k + 63) / 64 little-endian 64-bit words, bit l
+ *                    of word w multiplying message bit 64 w + l; bits beyond k must be 0.  Parity i of a codeword is the GF(2) dot
+ *                    product of row i (block1's rows, then block2's) with the message.  With `systematic` the codeword is the k
+ *                    message bits followed by the m1 + m2 parities (P1 and P2 of a triangularised H, or the parity part of a
+ *                    systematic G); without, it is the m1 + m2 products alone (the rows of G^T).
+ *   SSF_ENC_SPARSE   the DVB-S2 accumulator: indptr (m1 + 1) and indices (nnz) are the CSR of A = H[:, :k], int32; the codeword is the
+ *                    message followed by cw[k + i] = (XOR of the message bits in row i of A) ^ cw[k + i - 1].  Rows may be empty.
+ * Checked before anything is uploaded: 1 <= k, 1 <= m1 (dense: k <= 32 768, sparse: k <= 131 072 and m1 <= 262 144), indptr rises from 0 to nnz,
+ * every index is in 0 .. k - 1. */
+enum ssf_enc_form { SSF_ENC_DENSE = 0, SSF_ENC_SPARSE = 1 };
+typedef struct {
+    int32_t form;                 /* ssf_enc_form */
+    int32_t k;                    /* message bits */
+    int32_t m1, m2;               /* dense: rows of block1 and block2; sparse: m1 checks, m2 = 0 */
+    int32_t systematic;           /* dense only */
+    int32_t nnz;                  /* sparse only */
+} ssf_ldpc_encoder_desc;
+typedef struct ssf_ldpc_encoder ssf_ldpc_encoder;
+int  ssf_ldpc_encoder_create(int device, const ssf_ldpc_encoder_desc *desc, const uint64_t *block1, const uint64_t *block2,
+                             const int32_t *indptr, const int32_t *indices, ssf_ldpc_encoder **out);
+int  ssf_ldpc_encoder_destroy(ssf_ldpc_encoder *encoder);
+/* bits_in (k, numCodewords) row-major -- or (numCodewords, k) with transposed = 1 -- one byte per bit, taken as b & 1, host or
+ * device, never written; codewords_out (n, numCodewords) or (numCodewords, n) bytes of 0 / 1, host or device: the first n rows of
+ * the codeword (n below its full length punctures it, as the reference crops to param.n).  1 <= numCodewords <= 65 535.
+ * One launch per call: a workgroup packs its messages into LDS and then owns 256 parity rows of 16 codewords (dense), or the whole
+ * scan of one codeword (sparse). */
+typedef struct {
+    int32_t numCodewords;
+    int32_t n;                    /* rows returned per codeword, 1 .. the codeword's length */
+    int32_t transposed;
+    int32_t reserved;
+} ssf_ldpc_encode_params;
+int  ssf_ldpc_encode(int device, const ssf_ldpc_encoder *encoder, const ssf_ldpc_encode_params *params, const void *bits_in,
+                     void *codewords_out);
+/* symb_out[i] = const_tab[sum_j (bits[i b + j] & 1) << (b - 1 - j)], b = log2 M: nsymb complex128 values, host or device;
+ * bits: nsymb b bytes, host or device; const_tab: M (re, im) pairs in the order of their labels, host.  M a power of two, 2 .. 1024 */
+int  ssf_modulate(int device, int64_t nsymb, int32_t M, const double *const_tab, const void *bits, void *symb_out);
+
 #ifdef __cplusplus
 }
 #endif

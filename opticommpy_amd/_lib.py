@@ -136,6 +136,29 @@ def fec_lds_bytes(E, n, prec):
     return ((E + (E >> 5) + 1) + 2 * n) * w + 16 + ((n + 15) // 16) * 16
 
 
+class EncoderDesc(C.Structure):
+    """ssf_ldpc_encoder_desc (include/ssf.h)."""
+    _fields_ = [("form", C.c_int32), ("k", C.c_int32), ("m1", C.c_int32), ("m2", C.c_int32), ("systematic", C.c_int32),
+                ("nnz", C.c_int32)]
+
+
+class EncodeParams(C.Structure):
+    """ssf_ldpc_encode_params (include/ssf.h)."""
+    _fields_ = [("numCodewords", C.c_int32), ("n", C.c_int32), ("transposed", C.c_int32), ("reserved", C.c_int32)]
+
+
+ENC_DENSE, ENC_SPARSE = 0, 1                                                                # ssf_enc_form
+ENC_TILE = 16              # codewords whose packed messages share a workgroup of the dense encoder (enc_kernels.h: kTile)
+ENC_ROWS = 256             # parity rows per workgroup of the dense encoder, one per lane (kRows)
+ENC_WAVE_SPAN = 64         # checks the accumulator scans with one ballot (kWave)
+ENC_SPAN = 256             # checks whose parities a workgroup of the accumulator takes in one pass (kSpan)
+ENC_CARRY_SPAN = 64 * 64   # checks whose 64 ballots get their carries from one ballot of totals (kWave * kWave)
+ENC_BLOCK = 256            # lanes per workgroup of every encoder kernel, modulateGray's included (kBlock)
+ENC_MAX_K_DENSE = 32768    # message bits of the dense form: 16 packed messages in 64 KiB of LDS (kMaxWordsDense)
+ENC_MAX_K_SPARSE = 131072  # message bits of the sparse form (kMaxWordsSparse)
+ENC_MAX_M_SPARSE = 262144  # checks of the sparse form (kMaxChecksSparse)
+
+
 EQ_ALGS = {"nlms": 0, "cma": 1, "rde": 2, "da-rde": 3, "dd-lms": 4, "static": 5}             # ssf_eq_alg
 EQ_CHUNK = 64              # output symbols the serial equalizer kernel stages per chunk (eq_kernels.h: kChunk)
 EQ_STAGE_ELEMS = 1024      # ... unless ((c - 1) SpS + nTaps) nModes input values would exceed its staging buffer (kStageElems)
@@ -231,6 +254,11 @@ SYMBOLS = {
     "ssf_ldpc_graph_destroy": (C.c_int, [C.c_void_p]),
     "ssf_ldpc_decode": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(LdpcParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p]),
+    "ssf_ldpc_encoder_create": (C.c_int, [C.c_int, C.POINTER(EncoderDesc), C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), C.POINTER(C.c_void_p)]),
+    "ssf_ldpc_encoder_destroy": (C.c_int, [C.c_void_p]),
+    "ssf_ldpc_encode": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(EncodeParams), C.c_void_p, C.c_void_p]),
+    "ssf_modulate": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "ssf_device_copy_bandwidth": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_linear_channel": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p]),

@@ -940,4 +940,68 @@ int ssf_ldpc_decode(int device, const ssf_ldpc_graph *graph, const ssf_ldpc_para
     return rc ? set_err(rc, "ssf_ldpc_decode: " + err) : SSF_OK;
 }
 
+// ---- LDPC encoding and Gray mapping (engine_enc.hip): the kernels index with the CSR unchecked, so nothing out of range gets in
+static const char *encoder_bad(const ssf_ldpc_encoder_desc *d, const uint64_t *block1, const uint64_t *block2, const int32_t *indptr,
+                               const int32_t *indices) {
+    if (d->k < 1 || d->m1 < 1 || d->m2 < 0) return "k and m1 must be positive, m2 not negative";
+    if (d->form == SSF_ENC_DENSE) {
+        if (d->k > 32768) return "the dense form takes k <= 32768";
+        if ((int64_t)d->m1 + d->m2 > (1 << 24)) return "too many parity rows";
+        if (!block1 || (d->m2 > 0 && !block2)) return "NULL parity block";
+        return nullptr;
+    }
+    if (d->form != SSF_ENC_SPARSE) return "form must be SSF_ENC_DENSE or SSF_ENC_SPARSE";
+    if (d->k > 131072 || d->m1 > 262144) return "the sparse form takes k <= 131072 and m1 <= 262144";
+    if (d->m2 != 0 || d->nnz < 0 || !indptr || (d->nnz > 0 && !indices)) return "the sparse form needs indptr, indices and m2 = 0";
+    if (indptr[0] != 0 || indptr[d->m1] != d->nnz) return "indptr must run from 0 to nnz";
+    for (int i = 0; i < d->m1; ++i)
+        if (indptr[i + 1] < indptr[i] || indptr[i + 1] > d->nnz) return "indptr must rise from 0 to nnz";
+    for (int e = 0; e < d->nnz; ++e)
+        if (indices[e] < 0 || indices[e] >= d->k) return "indices holds a column outside 0 .. k - 1";
+    return nullptr;
+}
+
+int ssf_ldpc_encoder_create(int device, const ssf_ldpc_encoder_desc *desc, const uint64_t *block1, const uint64_t *block2,
+                            const int32_t *indptr, const int32_t *indices, ssf_ldpc_encoder **out) {
+    if (!desc || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_ldpc_encoder_create: NULL argument");
+    *out = nullptr;
+    if (const char *msg = encoder_bad(desc, block1, block2, indptr, indices))
+        return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ldpc_encoder_create: ") + msg);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::enc_create(device, desc, block1, block2, indptr, indices, out, &err);
+    return rc ? set_err(rc, "ssf_ldpc_encoder_create: " + err) : SSF_OK;
+}
+
+int ssf_ldpc_encoder_destroy(ssf_ldpc_encoder *encoder) {
+    if (!encoder) return SSF_OK;
+    std::string err;
+    int rc = ssf::enc_destroy(encoder, &err);
+    return rc ? set_err(rc, "ssf_ldpc_encoder_destroy: " + err) : SSF_OK;
+}
+
+int ssf_ldpc_encode(int device, const ssf_ldpc_encoder *encoder, const ssf_ldpc_encode_params *p, const void *bits_in,
+                    void *codewords_out) {
+    if (!encoder || !p || !bits_in || !codewords_out) return set_err(SSF_ERR_BAD_ARG, "ssf_ldpc_encode: NULL argument");
+    const int64_t full = (int64_t)encoder->rows + (encoder->form == SSF_ENC_SPARSE || encoder->systematic ? encoder->k : 0);
+    const char *msg = nullptr;
+    if (p->numCodewords < 1 || p->numCodewords > 65535) msg = "numCodewords must be 1 .. 65535";
+    else if (p->n < 1 || p->n > full) msg = "n must be 1 .. the codeword's length";
+    else if (device != encoder->device) msg = "the encoder lives on another device";
+    if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ldpc_encode: ") + msg);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::enc_encode(device, encoder, p, bits_in, codewords_out, &err);
+    return rc ? set_err(rc, "ssf_ldpc_encode: " + err) : SSF_OK;
+}
+
+int ssf_modulate(int device, int64_t nsymb, int32_t M, const double *const_tab, const void *bits, void *symb_out) {
+    if (!const_tab || !bits || !symb_out || nsymb < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate: bad argument");
+    if (M < 2 || M > 1024 || (M & (M - 1))) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate: M must be a power of two, 2 .. 1024");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::enc_modulate(device, nsymb, M, const_tab, bits, symb_out, &err);
+    return rc ? set_err(rc, "ssf_modulate: " + err) : SSF_OK;
+}
+
 }  // extern "C"

@@ -70,6 +70,13 @@ struct ssf_ldpc_graph {
     int *d_all = nullptr, *d_co = nullptr, *d_ev = nullptr, *d_vo = nullptr, *d_ve = nullptr;
 };
 
+// the matrices of ssf_ldpc_encoder_create on their device: the parity rows as words (dense), or the CSR of A (sparse)
+struct ssf_ldpc_encoder {
+    int device = 0, form = 0, k = 0, rows = 0, W = 0, systematic = 0;
+    uint64_t *d_P = nullptr;
+    int *d_ptr = nullptr, *d_idx = nullptr;   // one allocation
+};
+
 struct ssf_plan {
     int device = 0;
     int64_t N = 0;
@@ -182,6 +189,13 @@ int fec_graph_create(int device, int m, int n, int E, const int32_t *co, const i
 int fec_graph_destroy(ssf_ldpc_graph *g, std::string *err);
 int fec_decode(int device, const ssf_ldpc_graph *g, const ssf_ldpc_params *p, const void *llr_in, void *llr_out, int8_t *bits_out,
                int8_t *fail_out, uint32_t *iter_out, std::string *err);
+
+// engine_enc.hip (arguments already checked by ssf_api.hip)
+int enc_create(int device, const ssf_ldpc_encoder_desc *d, const uint64_t *block1, const uint64_t *block2, const int32_t *indptr,
+               const int32_t *indices, ssf_ldpc_encoder **out, std::string *err);
+int enc_destroy(ssf_ldpc_encoder *e, std::string *err);
+int enc_encode(int device, const ssf_ldpc_encoder *e, const ssf_ldpc_encode_params *p, const void *bits_in, void *cw_out, std::string *err);
+int enc_modulate(int device, int64_t nsymb, int M, const double *table, const void *bits, void *symb_out, std::string *err);
 
 inline int fail(ssf_plan *p, int code, const std::string &msg) {
     if (p) p->err = msg;
