@@ -752,6 +752,41 @@ int  ssf_ldpc_encode(int device, const ssf_ldpc_encoder *encoder, const ssf_ldpc
  * bits: nsymb b bytes, host or device; const_tab: M (re, im) pairs in the order of their labels, host.  M a power of two, 2 .. 1024 */
 int  ssf_modulate(int device, int64_t nsymb, int32_t M, const double *const_tab, const void *bits, void *symb_out);
 
+/* ---- OFDM (optic/comm/ofdm.py: modulateOFDM, demodulateOFDM) -------------------------------------------------------------------------
+ * A frame has Nfft carriers, of which the first Ns are used (Ns = Nfft, or Nfft / 2 - 1 with Hermitian symmetry): Ni of them carry
+ * data, Np the pilot, the rest nothing.  The caller describes the carrier plan with small host tables of int32 (the library checks
+ * every entry: the kernels index with them); all arithmetic is double, complex64 is widened on load and rounded once on store.
+ * Transforms of 16 .. 8192 points with a power-of-two length run in registers and LDS, one launch; every other length goes through
+ * a batched rocFFT between two element-wise kernels (route = SSF_OFDM_ROCFFT asks for that at any length).
+ * plan_key: 0, or a number the caller gives to ONE set of tables for as long as the process lives -- a call that repeats the key
+ * (and the geometry) of the call before it on the same device reuses the tables that are there and uploads none. */
+enum ssf_ofdm_route { SSF_OFDM_AUTO = 0, SSF_OFDM_ROCFFT = 1 };
+typedef struct {
+    int64_t nframes;              /* >= 1; nframes * SpS * Nfft below 2^31 */
+    int32_t Nfft;                 /* 4 .. 2^20 */
+    int32_t G;                    /* cyclic prefix, 0 .. Nfft */
+    int32_t SpS;                  /* modulator: samples per symbol, 1 .. 64 (the demodulator takes one sample per symbol) */
+    int32_t Ns, Ni, Np;           /* carriers in use; data carriers >= 1; pilots (0, or >= 2) */
+    int32_t in_dtype, out_dtype;  /* SSF_C64 / SSF_C128 (the demodulator's output has in_dtype) */
+    int32_t route;                /* ssf_ofdm_route */
+    int32_t reserved;
+    double  pilot_re, pilot_im;   /* the pilot symbol (the modulator rounds it to single precision, as the reference's frame does) */
+    uint64_t plan_key;
+} ssf_ofdm_params;
+/* src_map: SpS * Nfft codes, one per input k of the inverse transform (after zero padding and fftshift): 0 nothing,
+ * 1 + 8 d data symbol d of the frame, 2 the pilot, + 4 the conjugate of that.  symb: nframes * Ni values of in_dtype, host or device,
+ * never written (rounded to single precision where it is complex128: the reference's frame is complex64).  out: nframes *
+ * SpS * (Nfft + G) samples of out_dtype, host or device: ifft * sqrt(SpS * Nfft) with the last SpS * G samples in front. */
+int  ssf_ofdm_modulate(int device, const ssf_ofdm_params *params, const int32_t *src_map, const void *symb, void *out);
+/* sig: nframes * (Nfft + G) samples of in_dtype, host or device, never written.  bin_carrier: Nfft entries, the carrier 0 .. Ns - 1
+ * that bin k of fft(frame) is after fftshift (and the Hermitian slice), or -1.  data_carriers: Ni carriers in output order.
+ * With Np > 0: pilot_carriers, Np strictly rising, and pilot_hi, Ns entries in 1 .. Np - 1: carrier c lies on the line through the
+ * pilots pilot_hi[c] - 1 and pilot_hi[c] (the end segments run on).  The channel is the mean over the frames of |Y / pilot| and of
+ * its angle at the pilots, each joined by those lines; every frame is divided by it.  symb_out: nframes * Ni values of in_dtype;
+ * H_out: Ns complex128 values or NULL (not written when Np = 0); host or device. */
+int  ssf_ofdm_demodulate(int device, const ssf_ofdm_params *params, const int32_t *bin_carrier, const int32_t *data_carriers,
+                         const int32_t *pilot_carriers, const int32_t *pilot_hi, const void *sig, void *symb_out, void *H_out);
+
 #ifdef __cplusplus
 }
 #endif

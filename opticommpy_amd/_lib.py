@@ -159,6 +159,28 @@ ENC_MAX_K_SPARSE = 131072  # message bits of the sparse form (kMaxWordsSparse)
 ENC_MAX_M_SPARSE = 262144  # checks of the sparse form (kMaxChecksSparse)
 
 
+class OfdmParams(C.Structure):
+    """ssf_ofdm_params (include/ssf.h)."""
+    _fields_ = [("nframes", C.c_int64), ("Nfft", C.c_int32), ("G", C.c_int32), ("SpS", C.c_int32), ("Ns", C.c_int32), ("Ni", C.c_int32),
+                ("Np", C.c_int32), ("in_dtype", C.c_int32), ("out_dtype", C.c_int32), ("route", C.c_int32), ("reserved", C.c_int32),
+                ("pilot_re", C.c_double), ("pilot_im", C.c_double), ("plan_key", C.c_uint64)]
+
+
+OFDM_ROUTES = {"auto": 0, "rocfft": 1}                                                       # ssf_ofdm_route
+OFDM_SRC_ZERO, OFDM_SRC_DATA, OFDM_SRC_PILOT, OFDM_SRC_CONJ = 0, 1, 2, 4                     # the codes of src_map (ofdm_kernels.h)
+OFDM_MIN_LDS, OFDM_MAX_LDS = 16, 8192      # power-of-two transform lengths that run in registers and LDS (kMinLg, kMaxLg)
+
+
+def ofdm_lds_length(L):
+    """Whether a transform of L points runs in registers and LDS (ofdm_kernels.h: lds_length); every other length is rocFFT's."""
+    return OFDM_MIN_LDS <= L <= OFDM_MAX_LDS and L & (L - 1) == 0
+
+
+def ofdm_frames_per_workgroup(L):
+    """Frames a workgroup of the register-and-LDS kernels takes at L points (ofdm_kernels.h: frames_per_workgroup)."""
+    return max(256, L // 16) // (L // 16)
+
+
 EQ_ALGS = {"nlms": 0, "cma": 1, "rde": 2, "da-rde": 3, "dd-lms": 4, "static": 5}             # ssf_eq_alg
 EQ_CHUNK = 64              # output symbols the serial equalizer kernel stages per chunk (eq_kernels.h: kChunk)
 EQ_STAGE_ELEMS = 1024      # ... unless ((c - 1) SpS + nTaps) nModes input values would exceed its staging buffer (kStageElems)
@@ -259,6 +281,9 @@ SYMBOLS = {
     "ssf_ldpc_encoder_destroy": (C.c_int, [C.c_void_p]),
     "ssf_ldpc_encode": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(EncodeParams), C.c_void_p, C.c_void_p]),
     "ssf_modulate": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "ssf_ofdm_modulate": (C.c_int, [C.c_int, C.POINTER(OfdmParams), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "ssf_ofdm_demodulate": (C.c_int, [C.c_int, C.POINTER(OfdmParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssf_device_copy_bandwidth": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_linear_channel": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p]),

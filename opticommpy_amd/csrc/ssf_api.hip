@@ -1004,4 +1004,57 @@ int ssf_modulate(int device, int64_t nsymb, int32_t M, const double *const_tab, 
     return rc ? set_err(rc, "ssf_modulate: " + err) : SSF_OK;
 }
 
+// ---- OFDM (engine_ofdm.hip): the kernels index with the carrier tables unchecked, so nothing out of range gets in
+static const char *ofdm_bad(const ssf_ofdm_params *p, bool mod) {
+    if (p->nframes < 1) return "nframes must be positive";
+    if (p->Nfft < 4 || p->Nfft > (1 << 20)) return "Nfft must be 4 .. 2^20";
+    if (p->G < 0 || p->G > p->Nfft) return "G must be 0 .. Nfft";
+    if (mod && (p->SpS < 1 || p->SpS > 64)) return "SpS must be 1 .. 64";
+    if (p->Ns < 1 || p->Ns > p->Nfft) return "Ns must be 1 .. Nfft";
+    if (p->Np < 0 || p->Np == 1) return "Np must be 0 or at least 2";
+    if (p->Ni < 1 || (int64_t)p->Ni + p->Np > p->Ns) return "Ni must be 1 .. Ns - Np";
+    if ((p->in_dtype != SSF_C64 && p->in_dtype != SSF_C128) || (mod && p->out_dtype != SSF_C64 && p->out_dtype != SSF_C128))
+        return "dtype must be SSF_C64 or SSF_C128";
+    if (p->route != SSF_OFDM_AUTO && p->route != SSF_OFDM_ROCFFT) return "route must be SSF_OFDM_AUTO or SSF_OFDM_ROCFFT";
+    if (p->nframes * (mod ? p->SpS : 1) * (int64_t)p->Nfft >= (1ll << 31)) return "nframes * SpS * Nfft must stay below 2^31";
+    if (p->Np > 0 && p->pilot_re == 0.0 && p->pilot_im == 0.0) return "the pilot symbol must not be zero";
+    return nullptr;
+}
+
+int ssf_ofdm_modulate(int device, const ssf_ofdm_params *p, const int32_t *src_map, const void *symb, void *out) {
+    if (!p || !src_map || !symb || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_ofdm_modulate: NULL argument");
+    const char *msg = ofdm_bad(p, true);
+    for (int64_t k = 0; !msg && k < (int64_t)p->SpS * p->Nfft; ++k) {
+        const int32_t code = src_map[k], kind = code & 3;
+        if (code < 0 || kind == 3 || (kind != 1 && (code >> 3) != 0) || (kind == 0 && code != 0) || (kind == 1 && (code >> 3) >= p->Ni))
+            msg = "src_map holds a code that names no source";
+    }
+    if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ofdm_modulate: ") + msg);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::ofdm_modulate(device, p, src_map, symb, out, &err);
+    return rc ? set_err(rc, "ssf_ofdm_modulate: " + err) : SSF_OK;
+}
+
+int ssf_ofdm_demodulate(int device, const ssf_ofdm_params *p, const int32_t *bin_carrier, const int32_t *data_carriers,
+                        const int32_t *pilot_carriers, const int32_t *pilot_hi, const void *sig, void *symb_out, void *H_out) {
+    if (!p || !bin_carrier || !data_carriers || !sig || !symb_out) return set_err(SSF_ERR_BAD_ARG, "ssf_ofdm_demodulate: NULL argument");
+    const char *msg = ofdm_bad(p, false);
+    if (!msg && p->Np > 0 && (!pilot_carriers || !pilot_hi)) msg = "pilots need pilot_carriers and pilot_hi";
+    for (int k = 0; !msg && k < p->Nfft; ++k)
+        if (bin_carrier[k] < -1 || bin_carrier[k] >= p->Ns) msg = "bin_carrier holds a carrier outside -1 .. Ns - 1";
+    for (int d = 0; !msg && d < p->Ni; ++d)
+        if (data_carriers[d] < 0 || data_carriers[d] >= p->Ns) msg = "data_carriers holds a carrier outside 0 .. Ns - 1";
+    for (int j = 0; !msg && j < p->Np; ++j)
+        if (pilot_carriers[j] < 0 || pilot_carriers[j] >= p->Ns || (j > 0 && pilot_carriers[j] <= pilot_carriers[j - 1]))
+            msg = "pilot_carriers must rise strictly inside 0 .. Ns - 1";
+    for (int c = 0; !msg && p->Np > 0 && c < p->Ns; ++c)
+        if (pilot_hi[c] < 1 || pilot_hi[c] >= p->Np) msg = "pilot_hi holds a segment outside 1 .. Np - 1";
+    if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ofdm_demodulate: ") + msg);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::ofdm_demodulate(device, p, bin_carrier, data_carriers, pilot_carriers, pilot_hi, sig, symb_out, H_out, &err);
+    return rc ? set_err(rc, "ssf_ofdm_demodulate: " + err) : SSF_OK;
+}
+
 }  // extern "C"

@@ -197,6 +197,12 @@ int enc_destroy(ssf_ldpc_encoder *e, std::string *err);
 int enc_encode(int device, const ssf_ldpc_encoder *e, const ssf_ldpc_encode_params *p, const void *bits_in, void *cw_out, std::string *err);
 int enc_modulate(int device, int64_t nsymb, int M, const double *table, const void *bits, void *symb_out, std::string *err);
 
+// engine_ofdm.hip (arguments and tables already checked by ssf_api.hip)
+int ofdm_modulate(int device, const ssf_ofdm_params *p, const int32_t *src_map, const void *symb, void *out, std::string *err);
+int ofdm_demodulate(int device, const ssf_ofdm_params *p, const int32_t *bin_carrier, const int32_t *data_carriers,
+                    const int32_t *pilot_carriers, const int32_t *pilot_hi, const void *sig, void *symb_out, void *H_out,
+                    std::string *err);
+
 inline int fail(ssf_plan *p, int code, const std::string &msg) {
     if (p) p->err = msg;
     return code;

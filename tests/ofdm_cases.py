@@ -1,0 +1,185 @@
+"""Shared by the OFDM tests: the fixtures tests/golden/ofdm/*.npz (tools/gen_golden_ofdm.py), the conditions every fixture must meet
+so that no test passes emptily, the parameter objects the tests hand to ``modulateOFDM`` / ``demodulateOFDM``, the bounds, and the
+files the emulator (tests/emu/emu_ofdm.cpp) reads and writes.
+
+The bounds (all relative to the largest entry of what is compared against):
+    modulator, complex64, against the restatement rounded to complex64      2^-23: one single-precision unit of the largest sample,
+                                                                            two roundings of nearly equal doubles
+    modulator, dtype=complex128, against the unrounded restatement          1e-12
+    modulator against the reference's recorded output                       the fixture's dist_mod + 2^-23 (triangle inequality)
+    demodulator, complex128: symbols and H                                  1e-9, the standing bound of the double paths
+    demodulator, complex64, against the reference's complex64 output        4 x the fixture's dist_dem64 (dist_H64 for H)
+    demodulator, complex64, against the restatement rounded once            2^-23"""
+import json
+import os
+import subprocess
+
+import numpy as np
+
+import ofdm_restatement as rs
+from opticommpy_amd import ofdm
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "ofdm")
+CASES = ["n250_sps2", "n255_sps3", "n512_sps4", "nb_hermit", "nb_nopilot", "nb_pilots", "one_frame", "unsorted"]
+EPS32 = 2.0 ** -23
+TOL_MOD128 = 1e-12
+TOL_DEMOD128 = 1e-9
+CHANNEL = np.array([1, 0.2 + 0.1j, 0.05])
+
+
+class Param:
+    """Stand-in for the reference's parameters object: attributes only."""
+
+    def __init__(self, **kw):
+        for k, v in kw.items():
+            setattr(self, k, v)
+
+
+_LOADED = {}
+
+
+def load(name):
+    """A fixture, read once and shared (nobody writes to it)."""
+    if name not in _LOADED:
+        z = np.load(os.path.join(GOLDEN, f"{name}.npz"))
+        g = {k: z[k] for k in z.files}
+        g["cfg"] = json.loads(str(g["cfg"]))
+        for a in g.values():
+            if isinstance(a, np.ndarray):
+                a.setflags(write=False)
+        _LOADED[name] = g
+    return _LOADED[name]
+
+
+def kwargs(g):
+    """The parameters as the restatement takes them."""
+    c = g["cfg"]
+    return dict(Nfft=c["Nfft"], G=c["G"], hermitSymmetry=c["hermitSymmetry"], pilot=complex(*c["pilot"]), SpS=c["SpS"],
+                pilotCarriers=c["pilotCarriers"], nullCarriers=c["nullCarriers"])
+
+
+def param(g, **kw):
+    k = kwargs(g)
+    k["pilotCarriers"] = np.array(k["pilotCarriers"], dtype=np.int64)
+    k["nullCarriers"] = np.array(k["nullCarriers"], dtype=np.int64)
+    k.update(kw)
+    return Param(**k)
+
+
+def rel(got, want):
+    """max |got - want| over the largest entry of want."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    return float(np.max(np.abs(got.astype(np.complex128) - want.astype(np.complex128))) / np.max(np.abs(want)))
+
+
+def check_conditions(g):
+    """What the generator promised, re-asserted on the stored arrays."""
+    c = g["cfg"]
+    Ns, data = rs.layout(c["Nfft"], c["hermitSymmetry"], c["pilotCarriers"], c["nullCarriers"])
+    F = c["frames"]
+    assert g["symb"].shape == (F * len(data),) and len(np.unique(g["symb"])) > 8                 # the data are not constant
+    assert g["tx"].dtype == np.complex64 and g["tx"].shape == (F * c["SpS"] * (c["Nfft"] + c["G"]),)
+    assert g["rx"].dtype == np.complex128 and g["rx"].shape == (F * (c["Nfft"] + c["G"]),)
+    want = np.convolve(np.sqrt(c["SpS"]) * g["tx"][::c["SpS"]].astype(np.complex128), CHANNEL)[:len(g["rx"])]
+    assert np.array_equal(g["rx"], want)
+    assert g["dem128"].dtype == np.complex128 and g["dem64"].dtype == np.complex64 and g["dem128"].shape == g["symb"].shape
+    assert 0 < float(g["dist_mod"]) < 3e-7 and 0 < float(g["dist_dem64"]) < 5e-7
+    if c["pilotCarriers"]:
+        assert g["H128"].shape == (Ns,) and g["H64"].shape == (Ns,)
+        Y = np.array([np.fft.fftshift(np.fft.fft(fr[c["G"]:])) / np.sqrt(c["Nfft"]) for fr in g["rx"].reshape(F, -1)])
+        if c["hermitSymmetry"]:
+            Y = Y[:, 1:1 + Ns]
+        est = Y[:, c["pilotCarriers"]] / complex(*c["pilot"])
+        assert np.max(np.abs(np.angle(est))) <= 0.5 and np.min(np.abs(est)) >= 0.5
+    else:
+        assert g["H128"].shape == (1,) and g["H128"][0] == 0
+
+
+def check_mod(g, got, dtype):
+    """A modulator output for the fixture's symbols against the restatement and the reference, at the bounds above; the figures."""
+    want = rs.modulate(g["symb"], **kwargs(g))
+    peak = np.max(np.abs(want))
+    if np.dtype(dtype) == np.complex128:
+        d = rel(got, want)
+        assert got.dtype == np.complex128 and d <= TOL_MOD128, d
+        return dict(restatement=d)
+    d = rel(got, want.astype(np.complex64))
+    r = float(np.max(np.abs(got.astype(np.complex128) - g["tx"].astype(np.complex128))) / peak)
+    assert got.dtype == np.complex64 and d <= EPS32, d
+    assert r <= float(g["dist_mod"]) + EPS32, (r, float(g["dist_mod"]))
+    return dict(restatement=d, reference=r)
+
+
+def check_demod(g, got, H, dtype):
+    """A demodulator output for the fixture's signal (cast to ``dtype``) against the reference and the restatement."""
+    Np = len(g["cfg"]["pilotCarriers"])
+    out = {}
+    if np.dtype(dtype) == np.complex128:
+        out["symbols"] = rel(got, g["dem128"])
+        assert got.dtype == np.complex128 and out["symbols"] <= TOL_DEMOD128, out
+        if Np:
+            out["H"] = rel(H, g["H128"])
+            assert H.dtype == np.complex128 and out["H"] <= TOL_DEMOD128, out
+    else:
+        want, Hw = rs.demodulate(g["rx"].astype(np.complex64), **kwargs(g))
+        out["symbols"] = rel(got, g["dem64"])
+        out["restatement"] = rel(got, want.astype(np.complex64))
+        assert got.dtype == np.complex64 and out["symbols"] <= 4 * float(g["dist_dem64"]), (out, float(g["dist_dem64"]))
+        assert out["restatement"] <= EPS32, out
+        if Np:
+            out["H"] = rel(H, g["H64"])
+            assert H.dtype == np.complex128 and out["H"] <= 4 * float(g["dist_H64"]), (out, float(g["dist_H64"]))
+            assert rel(H, Hw) <= TOL_DEMOD128
+    if not Np:
+        assert isinstance(H, complex) and H == 0
+    return out
+
+
+# ---- the emulator's files (tests/emu/emu_ofdm.cpp)
+def build_emu(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("emu_ofdm") / "emu_ofdm"
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-Wno-unknown-pragmas", "-I", os.path.join(ROOT, "opticommpy_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "emu", "emu_ofdm.cpp"), "-o", str(exe)])
+    return str(exe)
+
+
+def run_emu_mod(exe, tmp, symb, prm, dtype=np.complex64, route="auto"):
+    """``modulateOFDM`` with the kernels walked on the CPU: the host side is the package's own (``ofdm._prepare_mod``)."""
+    q = ofdm._prepare_mod(symb, prm, dtype, route)
+    p, x = q["plan"], q["x"]
+    with open(tmp / "in.bin", "wb") as f:
+        f.write(np.array([p["Nfft"], q["G"], p["SpS"], p["Ni"], x.dtype == np.complex64, q["dtype"] == np.complex64, q["route"]],
+                         dtype=np.int32).tobytes())
+        f.write(np.array([q["nframes"]], dtype=np.int64).tobytes())
+        f.write(np.array([q["pilot"].real, q["pilot"].imag], dtype=np.float64).tobytes())
+        f.write(p["src_map"].tobytes())
+        f.write(x.tobytes())
+    subprocess.check_call([exe, "mod", str(tmp / "in.bin"), str(tmp / "out.bin")])
+    out = np.fromfile(tmp / "out.bin", dtype=q["dtype"])
+    assert out.shape == (q["nout"],)
+    return out
+
+
+def run_emu_demod(exe, tmp, sig, prm, route="auto"):
+    """``demodulateOFDM`` (with ``returnChannel``) with the kernels walked on the CPU."""
+    q = ofdm._prepare_demod(sig, prm, route)
+    p, x = q["plan"], q["x"]
+    with open(tmp / "in.bin", "wb") as f:
+        f.write(np.array([p["Nfft"], q["G"], p["Ns"], p["Ni"], p["Np"], x.dtype == np.complex64, q["route"]], dtype=np.int32).tobytes())
+        f.write(np.array([q["nframes"]], dtype=np.int64).tobytes())
+        f.write(np.array([q["pilot"].real, q["pilot"].imag], dtype=np.float64).tobytes())
+        f.write(p["bin_carrier"].tobytes())
+        f.write(p["data"].tobytes())
+        if p["Np"]:
+            f.write(p["pilots"].tobytes())
+            f.write(p["hi"].tobytes())
+        f.write(x.tobytes())
+    subprocess.check_call([exe, "demod", str(tmp / "in.bin"), str(tmp / "out.bin")])
+    raw = open(tmp / "out.bin", "rb").read()
+    n = q["nframes"] * p["Ni"] * x.dtype.itemsize
+    out = np.frombuffer(raw[:n], dtype=x.dtype).copy()
+    H = np.frombuffer(raw[n:], dtype=np.complex128).copy() if p["Np"] else 0j
+    assert not p["Np"] or H.shape == (p["Ns"],)
+    return out, H
