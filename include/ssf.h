@@ -787,6 +787,43 @@ int  ssf_ofdm_modulate(int device, const ssf_ofdm_params *params, const int32_t 
 int  ssf_ofdm_demodulate(int device, const ssf_ofdm_params *params, const int32_t *bin_carrier, const int32_t *data_carriers,
                          const int32_t *pilot_carriers, const int32_t *pilot_hi, const void *sig, void *symb_out, void *H_out);
 
+/* ---- first-order perturbation model of the intrachannel NLIN (optic/models/perturbation.py: calcNLINperturbation,
+ * calcNLINperturbationSimplified, perturbationNLIN) ------------------------------------------------------------------------------
+ * With m = j - L, n = L - i and the symbols zero outside 0 .. n - 1 the reference's sum over its (2L+1)^2 window is
+ *     dx[t] = sum_m x[t+m] sum_n C_ifwm[L-n, L+m] P[t+n, m] + x[t] sum_n C_ixpm[L-n, L] |y[t+n]|^2,   P[s, m] = x[s] conj(x[s+m]) + y[s] conj(y[s+m])
+ * (dy with x and y exchanged).  The caller describes the coefficients as a plan of host tables (the library checks every entry):
+ *   pass      npass x {kind, m, first, count}: one inner sum over n.  kind 0: the line P[., m], the result times x[t+m] to dx and
+ *             times y[t+m] to dy; kind 1: the line |y|^2, times x[t] to dx; kind 2: the line |x|^2, times y[t] to dy (m = 0 for both).
+ *             Its coefficients are coef[first .. first + count).  dense: count = 2L+1 and coefficient k belongs to n = k - L;
+ *             else to n = nidx[first + k], -L .. L, rising strictly within the pass (so count <= 2L+1 either way).
+ *   coef      ncoef (re, im) pairs;  nidx: ncoef int32 (not read when dense, may be NULL)
+ *   phase_m, phase_c   nphase values of m, -L .. L, and (re, im) coefficients:
+ *             phi_x[t] = sum_k Im(phase_c[k]) (2 |x[t+m_k]|^2 + |y[t+m_k]|^2) + Im(ispm) (|x[t+o]|^2 + |y[t+o]|^2), o = ispm_offset
+ * entry SSF_NLIN_CALC: x, y are n values of in_dtype each; each is divided by the root of its mean power (rounded to single precision
+ * where in_dtype or prec is SSF_C64); out0 = dx, out1 = dy: n values of prec; out2 = phi_x, out3 = phi_y: n doubles.
+ * entry SSF_NLIN_FIELD: x is the (n, 2) field of in_dtype, y NULL; every column is normalised to unit power and then as above;
+ * out0 = nlin, (n, 2) of in_dtype: sqrt(P) E (e^{j P phi} - 1) + P^{3/2} d e^{j P phi} with P = peak_power, E the column after the
+ * first normalisation; out1 .. out3 NULL.  All arrays host or device, inputs never written.  All sums run in double in a fixed
+ * order.  plan_key: 0, or a number the caller gives to ONE set of tables for as long as the process lives -- a call that names a
+ * key the device still holds (the last 8, with the same L and counts; they live as long as the process) uploads no table. */
+enum ssf_nlin_entry { SSF_NLIN_CALC = 0, SSF_NLIN_FIELD = 1 };
+typedef struct {
+    int64_t n;                    /* symbols, 1 .. 2^32 */
+    int32_t L;                    /* matrix order, 1 .. 128 */
+    int32_t npass, ncoef, nphase; /* >= 0; npass <= 2L + 3, ncoef <= (2L + 3)(2L + 1), nphase <= 2L + 1 */
+    int32_t dense;                /* 0 / 1 */
+    int32_t entry;                /* ssf_nlin_entry */
+    int32_t in_dtype, prec;       /* SSF_C64 / SSF_C128 */
+    int32_t ispm_offset;          /* -L .. L */
+    int32_t reserved;
+    double  ispm_re, ispm_im;     /* C_ispm */
+    double  peak_power;           /* SSF_NLIN_FIELD: half the launch power [W] */
+    uint64_t plan_key;
+} ssf_nlin_params;
+int  ssf_pert_nlin(int device, const ssf_nlin_params *params, const int32_t *pass, const double *coef, const int32_t *nidx,
+                   const int32_t *phase_m, const double *phase_c, const void *x, const void *y, void *out0, void *out1, void *out2,
+                   void *out3);
+
 #ifdef __cplusplus
 }
 #endif

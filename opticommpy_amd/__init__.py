@@ -29,6 +29,7 @@ from .sync import finddelay, symbolSync  # noqa: F401
 from .equalization import mimoAdaptEqualizer  # noqa: F401
 from .fec import calcLLR, decodeLDPC, encodeLDPC, modulateGray, par2gen, readAlist, triangP1P2, writeAlist  # noqa: F401
 from .ofdm import calcSymbolRate, demodulateOFDM, hermit, modulateOFDM, zeroPad  # noqa: F401
+from .perturbation import calcNLINperturbation, calcNLINperturbationSimplified, calcPertCoeffMatrix, perturbationNLIN  # noqa: F401
 
 __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMapping", "DeviceArray", "to_device", "firFilter", "lowPassFIR", "decimate", "delaySignal", "iqMixing", "pbs", "photodiode", "balancedPD",
            "opticalHybrid2x4", "coherentReceiver", "pdmCoherentReceiver", "pdmCoherentReceiverChain", "parameters", "ssfm", "manakovSSF", "manakovDBP", "nlinPhaseRot", "convergenceCondition", "edfa", "edc", "blockwiseFFTConv", "linearFiberChannel",
@@ -36,4 +37,5 @@ __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMa
            "metrics", "fastBERcalc", "monteCarloGMI", "monteCarloMI", "calcEVM", "demodulateGray", "pnorm", "signalPower",
            "cpr", "bps", "bpsGPU", "fourthPowerFOE", "symbolSync", "finddelay", "mimoAdaptEqualizer", "calcLLR", "decodeLDPC", "readAlist",
            "encodeLDPC", "modulateGray", "par2gen", "triangP1P2", "writeAlist",
-           "modulateOFDM", "demodulateOFDM", "hermit", "zeroPad", "calcSymbolRate"]
+           "modulateOFDM", "demodulateOFDM", "hermit", "zeroPad", "calcSymbolRate",
+           "calcPertCoeffMatrix", "calcNLINperturbation", "calcNLINperturbationSimplified", "perturbationNLIN"]

@@ -181,6 +181,28 @@ def ofdm_frames_per_workgroup(L):
     return max(256, L // 16) // (L // 16)
 
 
+class NlinParams(C.Structure):
+    """ssf_nlin_params (include/ssf.h)."""
+    _fields_ = [("n", C.c_int64), ("L", C.c_int32), ("npass", C.c_int32), ("ncoef", C.c_int32), ("nphase", C.c_int32),
+                ("dense", C.c_int32), ("entry", C.c_int32), ("in_dtype", C.c_int32), ("prec", C.c_int32), ("ispm_offset", C.c_int32),
+                ("reserved", C.c_int32), ("ispm_re", C.c_double), ("ispm_im", C.c_double), ("peak_power", C.c_double),
+                ("plan_key", C.c_uint64)]
+
+
+NLIN_CALC, NLIN_FIELD = 0, 1                                                                 # ssf_nlin_entry
+NLIN_MAX_ORDER = 128       # largest matrixOrder (nlin_kernels.h: kMaxL)
+NLIN_OUT = 4               # consecutive outputs a lane of the main kernel holds (kOut)
+NLIN_TILE = 256            # symbols per workgroup of the main kernel (kTile = kLanes kOut)
+NLIN_MAX_SPLIT = 16        # most shares the passes of a plan are dealt into (kMaxSplit)
+NLIN_TARGET_GROUPS = 2048  # workgroups the main kernel aims at (kTargetGroups)
+
+
+def nlin_split(n, npass):
+    """Shares the passes are dealt into for n symbols (nlin_kernels.h: split_for)."""
+    tiles = (n + NLIN_TILE - 1) // NLIN_TILE
+    return min((NLIN_TARGET_GROUPS + tiles - 1) // tiles, NLIN_MAX_SPLIT, npass)
+
+
 EQ_ALGS = {"nlms": 0, "cma": 1, "rde": 2, "da-rde": 3, "dd-lms": 4, "static": 5}             # ssf_eq_alg
 EQ_CHUNK = 64              # output symbols the serial equalizer kernel stages per chunk (eq_kernels.h: kChunk)
 EQ_STAGE_ELEMS = 1024      # ... unless ((c - 1) SpS + nTaps) nModes input values would exceed its staging buffer (kStageElems)
@@ -284,6 +306,8 @@ SYMBOLS = {
     "ssf_ofdm_modulate": (C.c_int, [C.c_int, C.POINTER(OfdmParams), C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
     "ssf_ofdm_demodulate": (C.c_int, [C.c_int, C.POINTER(OfdmParams), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_pert_nlin": (C.c_int, [C.c_int, C.POINTER(NlinParams), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssf_device_copy_bandwidth": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_linear_channel": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p]),

@@ -1057,4 +1057,45 @@ int ssf_ofdm_demodulate(int device, const ssf_ofdm_params *p, const int32_t *bin
     return rc ? set_err(rc, "ssf_ofdm_demodulate: " + err) : SSF_OK;
 }
 
+// ---- perturbation model (engine_nlin.hip): the kernels index LDS and the symbols with m and n unchecked, so nothing out of range gets in
+int ssf_pert_nlin(int device, const ssf_nlin_params *p, const int32_t *pass, const double *coef, const int32_t *nidx,
+                  const int32_t *phase_m, const double *phase_c, const void *x, const void *y, void *out0, void *out1, void *out2,
+                  void *out3) {
+    if (!p || !x || !out0) return set_err(SSF_ERR_BAD_ARG, "ssf_pert_nlin: NULL argument");
+    const char *msg = nullptr;
+    const int64_t L = p->L, W = 2 * L + 1;
+    if (p->n < 1 || p->n > (1ll << 32)) msg = "n must be 1 .. 2^32";
+    else if (L < 1 || L > 128) msg = "L must be 1 .. 128";
+    else if (p->npass < 0 || p->npass > W + 2 || p->ncoef < 0 || p->ncoef > (W + 2) * W || p->nphase < 0 || p->nphase > W)
+        msg = "npass, ncoef or nphase outside what a matrix of order 2L + 1 gives";
+    else if (p->dense != 0 && p->dense != 1) msg = "dense must be 0 or 1";
+    else if (p->entry != SSF_NLIN_CALC && p->entry != SSF_NLIN_FIELD) msg = "entry must be SSF_NLIN_CALC or SSF_NLIN_FIELD";
+    else if ((p->in_dtype != SSF_C64 && p->in_dtype != SSF_C128) || (p->prec != SSF_C64 && p->prec != SSF_C128))
+        msg = "dtype must be SSF_C64 or SSF_C128";
+    else if (p->ispm_offset < -L || p->ispm_offset > L) msg = "ispm_offset must be -L .. L";
+    else if (!std::isfinite(p->ispm_re) || !std::isfinite(p->ispm_im) || !std::isfinite(p->peak_power) || p->peak_power < 0.0)
+        msg = "ispm and peak_power must be finite, peak_power not negative";
+    else if (p->entry == SSF_NLIN_CALC && (!y || !out1 || !out2 || !out3)) msg = "SSF_NLIN_CALC needs y and four outputs";
+    else if ((p->npass && !pass) || (p->ncoef && !coef) || (p->ncoef && !p->dense && !nidx) || (p->nphase && (!phase_m || !phase_c)))
+        msg = "a table is missing";
+    for (int k = 0; !msg && k < p->npass; ++k) {
+        const int32_t kind = pass[4 * k], m = pass[4 * k + 1], first = pass[4 * k + 2], count = pass[4 * k + 3];
+        if (kind < 0 || kind > 2 || m < -L || m > L || (kind != 0 && m != 0)) msg = "pass holds a kind or an m out of range";
+        else if (first < 0 || count < 1 || (int64_t)first + count > p->ncoef) msg = "pass names coefficients outside coef";
+        else if (p->dense && count != W) msg = "a dense pass needs 2L + 1 coefficients";
+        else if (count > W) msg = "a pass holds more than 2L + 1 coefficients";           // its LDS slice holds no more
+        for (int32_t j = 0; !msg && !p->dense && j < count; ++j) {
+            if (nidx[first + j] < -L || nidx[first + j] > L) msg = "nidx holds an n outside -L .. L";
+            else if (j > 0 && nidx[first + j] <= nidx[first + j - 1]) msg = "the n of a pass must rise strictly";
+        }
+    }
+    for (int k = 0; !msg && k < p->nphase; ++k)
+        if (phase_m[k] < -L || phase_m[k] > L) msg = "phase_m holds an m outside -L .. L";
+    if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_pert_nlin: ") + msg);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::nlin_run(device, p, pass, coef, nidx, phase_m, phase_c, x, y, out0, out1, out2, out3, &err);
+    return rc ? set_err(rc, "ssf_pert_nlin: " + err) : SSF_OK;
+}
+
 }  // extern "C"

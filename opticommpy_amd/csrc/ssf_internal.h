@@ -203,6 +203,10 @@ int ofdm_demodulate(int device, const ssf_ofdm_params *p, const int32_t *bin_car
                     const int32_t *pilot_carriers, const int32_t *pilot_hi, const void *sig, void *symb_out, void *H_out,
                     std::string *err);
 
+// engine_nlin.hip (arguments and tables already checked by ssf_api.hip)
+int nlin_run(int device, const ssf_nlin_params *p, const int32_t *pass, const double *coef, const int32_t *nidx, const int32_t *phase_m,
+             const double *phase_c, const void *x, const void *y, void *out0, void *out1, void *out2, void *out3, std::string *err);
+
 inline int fail(ssf_plan *p, int code, const std::string &msg) {
     if (p) p->err = msg;
     return code;
