@@ -8,10 +8,14 @@
 //   int64 n, total, nref, nModes, nTaps, SpS, dtype, ref_dtype, nStages, numIter, M, nRadii;  double Rcma;
 //   per stage: int64 L, int64 alg, double mu;  double table[2 M];  double radii[nRadii];  complex128 H[nModes^2 nTaps];  x;  ref
 // output (binary): sigOut (total, nModes) complex128, H (nModes^2, nTaps) complex128, errSq (nModes, total) float64;
-// stdout: the seconds the loops took, without reading and writing the files (tools/bench_eq.py's CPU comparator)
+// stdout: the seconds the loops took, without reading and writing the files (tools/bench_eq.py's CPU comparator), then the
+// header's chunk_symbols and coeffs_per_lane for the geometry (the chunking itself is not emulated; tests/test_eq_shapes_emu.py
+// holds the two numbers to the rows' literals)
+// usage: emu_eq --nlms-scale <sum of squares as a hexadecimal float> ...   prints nlms_scale of each, as a hexadecimal float
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 #include "eq_kernels.h"
@@ -101,6 +105,10 @@ static void serial(const Problem &p, int k, const Seg &sg, Cplx *H, Cplx *y, dou
 }
 
 int main(int argc, char **argv) {
+    if (argc >= 2 && std::string(argv[1]) == "--nlms-scale") {       // nlms_scale of every further argument, bit for bit (%a)
+        for (int i = 2; i < argc; ++i) std::printf("%a\n", nlms_scale(std::strtod(argv[i], nullptr)));
+        return 0;
+    }
     if (argc != 3) return 2;
     FILE *f = std::fopen(argv[1], "rb");
     if (!f) return 2;
@@ -150,6 +158,7 @@ int main(int argc, char **argv) {
         }
     }
     std::printf("loop_s %.6f\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+    std::printf("chunk %d coeffs_per_lane %d\n", chunk_symbols(p.nModes, p.nTaps, p.SpS), R);
     FILE *o = std::fopen(argv[2], "wb");
     if (!o) return 2;
     std::fwrite(y.data(), 16, y.size(), o);

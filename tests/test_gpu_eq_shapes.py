@@ -7,14 +7,18 @@ staging chunk of the serial kernel.
 
 Bounds (tests/eq_cases.py): sigOut and H within 1e-9 rel-L2 and per element against max |ref|, errSq within 1e-9 of max |ref|.
 Every decision of a 'dd-lms' or 'rde' stage in the restatement has its two nearest candidates at least 1e-9 apart (asserted): the
-two computations agree to about 1e-15, so none can fall the other way."""
-import functools
+two computations agree to about 1e-15, so none can fall the other way.
 
+test_every_row_of_the_shape_table runs the named rows of tests/eq_shape_cases.py (tables wider than a wave, every pair of
+argument types at every number of coefficients per lane, lane counts either side of 64 .. 256, chunks shorter than 64, runs of
+8 .. 17 stages, the end of the signal, exact ties), each with numpy arguments and with DeviceArrays, which must agree bit for
+bit; tests/test_eq_shapes_emu.py runs the same rows through the g++ emulation."""
 import numpy as np
 import pytest
 
 import eq_cases as ec
 import eq_restatement as er
+import eq_shape_cases as sc
 import opticommpy_amd as oa
 from opticommpy_amd import _lib
 from opticommpy_amd import equalization as oeq
@@ -23,18 +27,7 @@ pytestmark = pytest.mark.gpu
 
 C = _lib.EQ_CHUNK
 ALL = ["nlms", "cma", "da-rde", "rde", "dd-lms"]
-
-
-@functools.lru_cache(maxsize=None)
-def signal(nsym, modes, sps, seed):
-    """16-QAM at sps samples per symbol, scaled, mixed between neighbouring modes, with a little noise; and its symbols."""
-    rng = np.random.default_rng(seed)
-    table = oeq._tables(16, "qam", 0, np.complex128)[0]
-    tx = table[rng.integers(0, 16, size=(nsym, modes))]
-    x = np.repeat(tx, sps, axis=0) * 0.9 + 0.04 * (rng.normal(size=(nsym * sps, modes)) + 1j * rng.normal(size=(nsym * sps, modes)))
-    x = x + 0.2 * np.exp(0.3j) * np.roll(x, 1, axis=1) if modes > 1 else x
-    x.setflags(write=False), tx.setflags(write=False)
-    return x, tx
+signal = sc.signal
 
 
 def check(x, prm, tx, label, device):
@@ -129,3 +122,43 @@ def test_more_adaptive_stages_than_one_launch_takes():
     alg = (ALL * 2)[:10]
     prm = ec.Param(alg=alg, mu=[3e-3] * 10, L=[13] * 10, nTaps=15, SpS=2, M=16, numIter=2, prec=np.complex128)
     check(x, prm, tx, "ten stages", device=True)
+
+
+def run_row(row, device, widen=False):
+    """(sigOut, H, errSq) of one call for a row (errSq None where the row asks for no results); inputs and param.H unwritten."""
+    x, prm, tx = sc.widened(row) if widen else sc.build(row)
+    x0, t0, H0 = x.copy(), tx.copy(), (prm.H.copy() if hasattr(prm, "H") else None)
+    dx, dt = (oa.to_device(x), oa.to_device(tx)) if device else (x, tx)
+    got = oa.mimoAdaptEqualizer(dx, prm, dt)
+    if prm.returnResults:
+        out, H, errSq, Hiter = got
+        assert np.array_equal(Hiter[:, :, 0], H) and H.dtype == np.complex128 and errSq.dtype == np.float64
+    else:
+        out, H, errSq = got, None, None
+    if device:
+        assert isinstance(out, oa.DeviceArray) and np.array_equal(dx.get(), x0) and np.array_equal(dt.get(), t0), row.id
+        out = out.get()
+    assert isinstance(out, np.ndarray) and out.dtype == np.complex128 and out.shape == sc.expected(row)[0].shape, row.id
+    assert np.array_equal(x, x0) and np.array_equal(tx, t0) and (H0 is None or np.array_equal(prm.H, H0)), row.id
+    return out, H, errSq
+
+
+def same_bits(a, b, label):
+    for u, v in zip(a, b):
+        assert (u is None and v is None) or np.array_equal(u, v), label
+
+
+@pytest.mark.parametrize("name", [r.id for r in sc.ROWS])
+def test_every_row_of_the_shape_table(name):
+    row = sc.BY_ID[name]
+    sc.check_conditions(row)
+    host, dev = run_row(row, device=False), run_row(row, device=True)
+    same_bits(host, dev, f"{name}: numpy arguments and DeviceArrays")
+    if "noresults" in row.opt:
+        sc.compare(row, host, "gpu", only_sigout=True)
+    else:
+        sc.compare(row, host, "gpu")
+    sc.zero_regions(row, host[0], host[2])
+    same_bits(host, run_row(row, device=True), f"{name}: a second call")
+    if row.xdtype != "complex128" or row.rdtype != "complex128":       # the same values widened on the host: the same bits
+        same_bits(host, run_row(row, device=False, widen=True), f"{name}: widened arguments")
