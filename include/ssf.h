@@ -824,6 +824,59 @@ int  ssf_pert_nlin(int device, const ssf_nlin_params *params, const int32_t *pas
                    const int32_t *phase_m, const double *phase_c, const void *x, const void *y, void *out0, void *out1, void *out2,
                    void *out3);
 
+/* ---- the sampling clock on the device: the converters that put a clock offset on a signal and the stage that takes it off
+ * (optic/dsp/core.py:272-349 clockSamplingInterp, quantizer; optic/models/devices.py:793-1022 adc, dac; optic/dsp/clockRecovery.py
+ * gardnerClockRecovery, calcClockDrift).  Arrays are (rows, ncols) row-major, host or device; inputs are never written.  Arithmetic
+ * is double, single-precision data are widened on load and rounded on store; the converters give numpy's results bit for bit.
+ *
+ * ssf_clock_interp: np.interp(tout, tin, x) per column with tin[j] = j inTs and tout[i] = i outTs, or the caller's n_out times
+ * t_re (host or device; NULL: computed).  form SSF_CLOCK_REAL: real data, numpy's real rule (the slope is a quotient);
+ * SSF_CLOCK_COMPLEX: complex data, numpy's complex rule (the slope is a product with a reciprocal), one time per output;
+ * SSF_CLOCK_COMPONENTS: complex data, each component by the real rule, the imaginary parts at the times t_im (NULL: t_re).
+ * Then, in the same pass: clip != 0: np.clip to [lo, hi] (complex data: to lo + 1j lo .. hi + 1j hi in numpy's lexicographic order
+ * of complex numbers); quantize != 0: every component to the nearest of qmin + i qdelta, i < qlevels (the first on a tie).
+ * out has x's dtype, or float64 / complex128 with quantize. */
+enum ssf_clock_form { SSF_CLOCK_REAL = 0, SSF_CLOCK_COMPLEX = 1, SSF_CLOCK_COMPONENTS = 2 };
+typedef struct {
+    int64_t n_in, n_out;          /* rows of x and of out; 1 <= n_in, 0 <= n_out */
+    int32_t ncols;
+    int32_t dtype;                /* ssf_metrics_dtype of x */
+    int32_t form;                 /* ssf_clock_form */
+    int32_t clip, quantize;       /* 0 / 1 */
+    int32_t reserved;
+    double  inTs, outTs;          /* > 0 */
+    double  lo, hi;               /* clip */
+    double  qmin, qdelta;         /* quantize: qdelta > 0 */
+    int64_t qlevels;              /* >= 1 */
+} ssf_clock_params;
+int  ssf_clock_interp(int device, const ssf_clock_params *params, const void *x, const double *t_re, const double *t_im, void *out);
+/* out[i] (float64) = the level nearest to x[i], count values of `dtype`; of a complex value the real part is quantised */
+int  ssf_quantize(int device, int64_t count, int32_t dtype, double qmin, double qdelta, int64_t qlevels, const void *x, double *out);
+/* np.clip(x, lo, hi) over count values of `dtype` (complex: the lexicographic clip above); out has x's dtype */
+int  ssf_clip(int device, int64_t count, int32_t dtype, double lo, double hi, const void *x, void *out);
+/* out2 (host) = {min, max} over the real and imaginary parts of count values; NaNs are passed over */
+int  ssf_minmax(int device, int64_t count, int32_t dtype, const void *x, double *out2);
+/* out = (x + noise) scale over count doubles; noise may be NULL; has_scale == 0: no product */
+int  ssf_clock_scale_add(int device, int64_t count, double scale, int32_t has_scale, const double *x, const double *noise, double *out);
+/* ssf_gardner: Gardner clock recovery with a PI loop filter, one wavefront per mode.  x: (n, nModes) complex128 or complex64, taken
+ * as followed by lpad rows of zeros.  sig_out: (Ln, nModes) complex64, t_out: (Ln, nModes) float64, both zero where the loop did
+ * not write; last_n (host): per mode the output index the loop ended at.  The arithmetic is the one tests/clock_restatement.py
+ * states (double state, outputs rounded to single, the detector on the rounded outputs).  SSF_ERR_UNSUPPORTED if a mode's loop falls
+ * back further behind its furthest output than the kernel keeps in LDS. */
+typedef struct {
+    int64_t n, lpad, Ln;          /* n >= 1, lpad >= 0, 1 <= Ln */
+    int32_t nModes;               /* 1 .. 65535 */
+    int32_t dtype;                /* SSF_M_C128 or SSF_M_C64 */
+    int32_t nyquist;              /* 1: gardnerTEDnyquist, 0: gardnerTED */
+    int32_t reserved;
+    double  kp, ki;
+} ssf_gardner_params;
+int  ssf_gardner(int device, const ssf_gardner_params *params, const void *x, void *sig_out, double *t_out, int64_t *last_n);
+/* calcClockDrift: per column of t (n, ncols) float64 the peaks of |diff(t - mean)| of height >= 0.5 (scipy.signal.find_peaks' rule)
+ * -> ppm_out[col] (host) = sign(mean) 1e6 (count - 1) / (last - first), NaN with fewer than two peaks.  The mean is taken over the
+ * whole array (per_column == 0, the reference's 2-D call) or over the column (the reference's call per 1-D column). */
+int  ssf_clock_drift(int device, int64_t n, int32_t ncols, int32_t per_column, const double *t, double *ppm_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,10 @@ from .equalization import mimoAdaptEqualizer  # noqa: F401
 from .fec import calcLLR, decodeLDPC, encodeLDPC, modulateGray, par2gen, readAlist, triangP1P2, writeAlist  # noqa: F401
 from .ofdm import calcSymbolRate, demodulateOFDM, hermit, modulateOFDM, zeroPad  # noqa: F401
 from .perturbation import calcNLINperturbation, calcNLINperturbationSimplified, calcPertCoeffMatrix, perturbationNLIN  # noqa: F401
+from . import clock  # noqa: F401
+from .clock import (  # noqa: F401
+    adc, calcClockDrift, clockSamplingInterp, dac, gardnerClockRecovery, gardnerTED, gardnerTEDnyquist, interpolator, quantizer, resample,
+)
 
 __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMapping", "DeviceArray", "to_device", "firFilter", "lowPassFIR", "decimate", "delaySignal", "iqMixing", "pbs", "photodiode", "balancedPD",
            "opticalHybrid2x4", "coherentReceiver", "pdmCoherentReceiver", "pdmCoherentReceiverChain", "parameters", "ssfm", "manakovSSF", "manakovDBP", "nlinPhaseRot", "convergenceCondition", "edfa", "edc", "blockwiseFFTConv", "linearFiberChannel",
@@ -38,4 +42,6 @@ __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMa
            "cpr", "bps", "bpsGPU", "fourthPowerFOE", "symbolSync", "finddelay", "mimoAdaptEqualizer", "calcLLR", "decodeLDPC", "readAlist",
            "encodeLDPC", "modulateGray", "par2gen", "triangP1P2", "writeAlist",
            "modulateOFDM", "demodulateOFDM", "hermit", "zeroPad", "calcSymbolRate",
-           "calcPertCoeffMatrix", "calcNLINperturbation", "calcNLINperturbationSimplified", "perturbationNLIN"]
+           "calcPertCoeffMatrix", "calcNLINperturbation", "calcNLINperturbationSimplified", "perturbationNLIN",
+           "clockSamplingInterp", "quantizer", "resample", "adc", "dac", "gardnerClockRecovery", "calcClockDrift", "gardnerTED",
+           "gardnerTEDnyquist", "interpolator"]

@@ -203,6 +203,28 @@ def nlin_split(n, npass):
     return min((NLIN_TARGET_GROUPS + tiles - 1) // tiles, NLIN_MAX_SPLIT, npass)
 
 
+class ClockParams(C.Structure):
+    """ssf_clock_params (include/ssf.h)."""
+    _fields_ = [("n_in", C.c_int64), ("n_out", C.c_int64), ("ncols", C.c_int32), ("dtype", C.c_int32), ("form", C.c_int32),
+                ("clip", C.c_int32), ("quantize", C.c_int32), ("reserved", C.c_int32), ("inTs", C.c_double), ("outTs", C.c_double),
+                ("lo", C.c_double), ("hi", C.c_double), ("qmin", C.c_double), ("qdelta", C.c_double), ("qlevels", C.c_int64)]
+
+
+class GardnerParams(C.Structure):
+    """ssf_gardner_params (include/ssf.h)."""
+    _fields_ = [("n", C.c_int64), ("lpad", C.c_int64), ("Ln", C.c_int64), ("nModes", C.c_int32), ("dtype", C.c_int32),
+                ("nyquist", C.c_int32), ("reserved", C.c_int32), ("kp", C.c_double), ("ki", C.c_double)]
+
+
+CLOCK_REAL, CLOCK_COMPLEX, CLOCK_COMPONENTS = 0, 1, 2                                        # ssf_clock_form
+CLOCK_BLOCK = 256          # lanes per workgroup of the element-wise passes and the reductions (clock_kernels.h: kBlock)
+CLOCK_MAX_BLOCKS = 4096    # workgroups of a grid-stride pass (kMaxBlocks)
+CLOCK_CHUNK = 256          # input samples per staging chunk of the clock recovery kernel (kChunk)
+CLOCK_RING = 256           # outputs of a column the clock recovery kernel holds in LDS (kRing)
+CLOCK_FLUSH = 64           # outputs that leave in one store (kFlush)
+CLOCK_LAG = 128            # ... once the loop is this far ahead of the first of them (kLag)
+
+
 EQ_ALGS = {"nlms": 0, "cma": 1, "rde": 2, "da-rde": 3, "dd-lms": 4, "static": 5}             # ssf_eq_alg
 EQ_CHUNK = 64              # output symbols the serial equalizer kernel stages per chunk (eq_kernels.h: kChunk)
 EQ_STAGE_ELEMS = 1024      # ... unless ((c - 1) SpS + nTaps) nModes input values would exceed its staging buffer (kStageElems)
@@ -308,6 +330,13 @@ SYMBOLS = {
                                       C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssf_pert_nlin": (C.c_int, [C.c_int, C.POINTER(NlinParams), C.POINTER(C.c_int32), C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_clock_interp": (C.c_int, [C.c_int, C.POINTER(ClockParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_quantize": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ssf_clip": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
+    "ssf_minmax": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
+    "ssf_clock_scale_add": (C.c_int, [C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_gardner": (C.c_int, [C.c_int, C.POINTER(GardnerParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    "ssf_clock_drift": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     "ssf_device_copy_bandwidth": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_linear_channel": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p]),

@@ -1098,4 +1098,85 @@ int ssf_pert_nlin(int device, const ssf_nlin_params *p, const int32_t *pass, con
     return rc ? set_err(rc, "ssf_pert_nlin: " + err) : SSF_OK;
 }
 
+// ---- the sampling clock (engine_clock.hip): every check comes before the first allocation, upload or launch
+static bool clock_bad_dtype(int32_t d) { return d < SSF_M_C128 || d > SSF_M_F32; }
+static bool clock_bad_table(double qmin, double qdelta, int64_t levels) {
+    return !std::isfinite(qmin) || !std::isfinite(qdelta) || !(qdelta > 0.0) || levels < 1;
+}
+
+int ssf_clock_interp(int device, const ssf_clock_params *p, const void *x, const double *t_re, const double *t_im, void *out) {
+    if (!p || !x || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_clock_interp: NULL argument");
+    const char *msg = nullptr;
+    const bool cplx = p->dtype == SSF_M_C128 || p->dtype == SSF_M_C64;
+    if (clock_bad_dtype(p->dtype)) msg = "unknown dtype";
+    else if (p->n_in < 1 || p->n_out < 0 || p->ncols < 1 || p->n_in > (1LL << 40) || p->n_out > (1LL << 40)) msg = "sizes out of range";
+    else if (p->form < SSF_CLOCK_REAL || p->form > SSF_CLOCK_COMPONENTS || cplx != (p->form != SSF_CLOCK_REAL)) msg = "form does not fit dtype";
+    else if (!(p->inTs > 0.0) || !(p->outTs > 0.0) || !std::isfinite(p->inTs) || !std::isfinite(p->outTs)) msg = "inTs and outTs must be positive";
+    else if (t_im && (!t_re || p->form != SSF_CLOCK_COMPONENTS)) msg = "t_im needs t_re and SSF_CLOCK_COMPONENTS";
+    else if (p->clip && !(p->lo <= p->hi)) msg = "clip needs lo <= hi";
+    else if (p->quantize && clock_bad_table(p->qmin, p->qdelta, p->qlevels)) msg = "bad quantizer table";
+    if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_clock_interp: ") + msg);
+    if (p->n_out == 0) return SSF_OK;
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::clock_interp(device, p, x, t_re, t_im, out, &err);
+    return rc ? set_err(rc, "ssf_clock_interp: " + err) : SSF_OK;
+}
+
+int ssf_quantize(int device, int64_t count, int32_t dtype, double qmin, double qdelta, int64_t qlevels, const void *x, double *out) {
+    if (!x || !out || count < 1 || clock_bad_dtype(dtype) || clock_bad_table(qmin, qdelta, qlevels))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_quantize: bad argument");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::clock_quantize(device, count, dtype, qmin, qdelta, qlevels, x, out, &err);
+    return rc ? set_err(rc, "ssf_quantize: " + err) : SSF_OK;
+}
+
+int ssf_clip(int device, int64_t count, int32_t dtype, double lo, double hi, const void *x, void *out) {
+    if (!x || !out || count < 1 || clock_bad_dtype(dtype) || !(lo <= hi)) return set_err(SSF_ERR_BAD_ARG, "ssf_clip: bad argument");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::clock_clip(device, count, dtype, lo, hi, x, out, &err);
+    return rc ? set_err(rc, "ssf_clip: " + err) : SSF_OK;
+}
+
+int ssf_minmax(int device, int64_t count, int32_t dtype, const void *x, double *out2) {
+    if (!x || !out2 || count < 1 || clock_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_minmax: bad argument");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::clock_minmax(device, count, dtype, x, out2, &err);
+    return rc ? set_err(rc, "ssf_minmax: " + err) : SSF_OK;
+}
+
+int ssf_clock_scale_add(int device, int64_t count, double scale, int32_t has_scale, const double *x, const double *noise, double *out) {
+    if (!x || !out || count < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_clock_scale_add: bad argument");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::clock_scale_add(device, count, scale, has_scale, x, noise, out, &err);
+    return rc ? set_err(rc, "ssf_clock_scale_add: " + err) : SSF_OK;
+}
+
+int ssf_gardner(int device, const ssf_gardner_params *p, const void *x, void *sig_out, double *t_out, int64_t *last_n) {
+    if (!p || !x || !sig_out || !t_out || !last_n) return set_err(SSF_ERR_BAD_ARG, "ssf_gardner: NULL argument");
+    const char *msg = nullptr;
+    if (p->dtype != SSF_M_C128 && p->dtype != SSF_M_C64) msg = "dtype must be complex128 or complex64";
+    else if (p->n < 1 || p->lpad < 0 || p->Ln < 1 || p->n > (1LL << 40) || p->lpad > (1LL << 40) || p->Ln > (1LL << 41))
+        msg = "n >= 1, lpad >= 0 and Ln >= 1 are needed";
+    else if (p->nModes < 1 || p->nModes > 65535) msg = "nModes must be 1 .. 65535";
+    else if (!std::isfinite(p->kp) || !std::isfinite(p->ki)) msg = "kp and ki must be finite";
+    if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_gardner: ") + msg);
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::clock_gardner(device, p, x, sig_out, t_out, last_n, &err);
+    return rc ? set_err(rc, "ssf_gardner: " + err) : SSF_OK;
+}
+
+int ssf_clock_drift(int device, int64_t n, int32_t ncols, int32_t per_column, const double *t, double *ppm_out) {
+    if (!t || !ppm_out || n < 1 || ncols < 1 || ncols > 65535 || n > (1LL << 40)) return set_err(SSF_ERR_BAD_ARG, "ssf_clock_drift: bad argument");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::clock_drift(device, n, ncols, per_column, t, ppm_out, &err);
+    return rc ? set_err(rc, "ssf_clock_drift: " + err) : SSF_OK;
+}
+
 }  // extern "C"

@@ -207,6 +207,19 @@ int ofdm_demodulate(int device, const ssf_ofdm_params *p, const int32_t *bin_car
 int nlin_run(int device, const ssf_nlin_params *p, const int32_t *pass, const double *coef, const int32_t *nidx, const int32_t *phase_m,
              const double *phase_c, const void *x, const void *y, void *out0, void *out1, void *out2, void *out3, std::string *err);
 
+// engine_clock.hip (arguments already checked by ssf_api.hip)
+int clock_interp(int device, const ssf_clock_params *p, const void *x, const double *t_re, const double *t_im, void *out,
+                 std::string *err);
+int clock_quantize(int device, int64_t count, int dtype, double qmin, double qdelta, int64_t levels, const void *x, double *out,
+                   std::string *err);
+int clock_clip(int device, int64_t count, int dtype, double lo, double hi, const void *x, void *out, std::string *err);
+int clock_minmax(int device, int64_t count, int dtype, const void *x, double *out2, std::string *err);
+int clock_scale_add(int device, int64_t count, double scale, int has_scale, const double *x, const double *noise, double *out,
+                    std::string *err);
+int clock_gardner(int device, const ssf_gardner_params *p, const void *x, void *sig_out, double *t_out, int64_t *last_n,
+                  std::string *err);
+int clock_drift(int device, int64_t n, int ncols, int per_column, const double *t, double *ppm_out, std::string *err);
+
 inline int fail(ssf_plan *p, int code, const std::string &msg) {
     if (p) p->err = msg;
     return code;
