@@ -49,7 +49,7 @@ MK_HD bool interp_locate(double t, double inTs, double inFs, long long N, long l
         j = 0;
         return true;
     }
-    if (!(t <= (double)(N - 1) * inTs)) {              // beyond the end (a NaN time ends here too)
+    if (!(t <= (double)(N - 1) * inTs)) {              // beyond the end (a NaN time ends here too: locate() marks it)
         j = N - 1;
         return true;
     }
@@ -66,16 +66,19 @@ MK_HD double interp_recip(double a, double b, double inv, double tj, double t) {
 struct Located {
     long long j;
     bool exact;
+    bool nan;                     // a NaN time among two or more input times: numpy hands the time itself on
     double t;
 };
 MK_HD Located locate(double t, double inTs, double inFs, long long N) {
     Located l;
     l.t = t;
+    l.nan = t != t && N > 1;      // (one input time: numpy compares, and a NaN that is neither below nor above gives x[0])
     l.exact = interp_locate(t, inTs, inFs, N, l.j);
     return l;
 }
 // component `comp` of the output located at l, from the samples a = x[j] and b = x[j + 1] of the column
 MK_HD double interp_component(const Located &l, const double *a, const double *b, int comp, double inTs, bool recip) {
+    if (l.nan) return recip && comp == 1 ? 0.0 : l.t;        // numpy's complex rule: NaN + 0j; its real rule: NaN
     if (l.exact) return a[comp];
     const double tj = (double)l.j * inTs, tj1 = (double)(l.j + 1) * inTs;
     return recip ? interp_recip(a[comp], b[comp], 1.0 / (tj1 - tj), tj, l.t) : interp_real(a[comp], b[comp], tj, tj1, l.t);
@@ -149,6 +152,7 @@ MK_HD void chain_element(const Chain &c, const void *x, const double *t_re, cons
             interp_samples(c.dtype, x, c.ncols, col, l, a, b);
         }
         im = round_to(single, interp_component(l, a, b, 1, c.inTs, recip));
+        if (c.form == kFormComponents && im != im) re = im;     // the parts are put together as re + 1j im: numpy's product 1j NaN is NaN + NaN j
     }
     if (c.clip) {
         if (cplx) clip_complex(re, im, c.lo, c.hi);

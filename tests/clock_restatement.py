@@ -82,10 +82,23 @@ def farrow(t):
     return c0, c1, c2, c3
 
 
+def fall_runs(g):
+    """The runs of consecutive steps back among a column's gaps (sign, n, m) as (n_peak, depth): while the loop steps back m stays
+    and n falls by one, so a run is a stretch of positive gaps with one m and n, n - 1, n - 2, ..."""
+    runs = []
+    for sign, n, m in g:
+        if sign > 0 and runs and runs[-1][2] == m and runs[-1][0] - runs[-1][1] == n:
+            runs[-1][1] += 1
+        elif sign > 0:
+            runs.append([n, 1, m])
+    return [(n, depth) for n, depth, _ in runs]
+
+
 def gardner(sigIn, kp=1e-3, ki=1e-6, isNyquist=True, lpad=1, maxPPM=500):
     """(sigOut, t_nco_values, info): the signal cut to [0:last_n] (1-D for 1-D input), the timing values not cut; info holds
     ``last_n`` per column, the indices ``gaps`` per column: the clock gaps the loop took,
     (sign, n, m) at the iteration that took it,
+    ``falls`` per column: every run of consecutive steps back as (n_peak, depth), the n at the first step back and the number of steps,
     ``dropped`` (columns whose last timing write fell on n == Ln) ``margin`` = min | |t_nco| - 1 | and ``tmax`` = max |t_nco| over the run (ahead of the gap decision)."""
     x = np.asarray(sigIn)
     input1D = x.ndim == 1
@@ -97,7 +110,7 @@ def gardner(sigIn, kp=1e-3, ki=1e-6, isNyquist=True, lpad=1, maxPPM=500):
     Ln = int((1 - maxPPM / 1e6) * nSamples)
     out = np.zeros((Ln, nModes), dtype=np.complex64)
     tv = np.zeros((Ln, nModes), dtype=np.float64)
-    last_n, lasts, gaps, dropped, margin, tmax = 0, [], [], [], np.inf, 0.0
+    last_n, lasts, gaps, falls, dropped, margin, tmax = 0, [], [], [], [], np.inf, 0.0
     for k in range(nModes):
         re = [float(v) for v in x[:, k].real] + [0.0] * lpad
         im = [float(v) for v in x[:, k].imag] + [0.0] * lpad
@@ -137,10 +150,11 @@ def gardner(sigIn, kp=1e-3, ki=1e-6, isNyquist=True, lpad=1, maxPPM=500):
         last_n = max(last_n, n)
         lasts.append(n)
         gaps.append(g)
+        falls.append(fall_runs(g))
     out = out[0:last_n, :]
     if input1D:
         out = out.flatten()
-    return out, tv, dict(last_n=lasts, gaps=gaps, dropped=dropped, margin=float(margin), tmax=float(tmax), Ln=Ln)
+    return out, tv, dict(last_n=lasts, gaps=gaps, falls=falls, dropped=dropped, margin=float(margin), tmax=float(tmax), Ln=Ln)
 
 
 # ---- clock drift

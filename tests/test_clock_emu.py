@@ -19,7 +19,7 @@ def test_constants_are_the_bindings(emu):
     k = cc.emu_constants(emu.exe)
     assert k == dict(chunk=_lib.CLOCK_CHUNK, win=_lib.CLOCK_CHUNK + 4, ring=_lib.CLOCK_RING, flush=_lib.CLOCK_FLUSH, lag=_lib.CLOCK_LAG,
                      block=_lib.CLOCK_BLOCK, max_blocks=_lib.CLOCK_MAX_BLOCKS)
-    assert (k["chunk"], k["flush"]) == (sc.C, sc.F) and k["lag"] + k["flush"] + 2 <= k["ring"]
+    assert (k["chunk"], k["flush"], k["lag"]) == (sc.C, sc.F, sc.LAG) and k["lag"] + k["flush"] + 2 <= k["ring"]
 
 
 @pytest.mark.parametrize("name", cc.INTERP)
@@ -62,32 +62,41 @@ def test_clock_recovery_fixtures(emu, name):
 def test_clock_recovery_rows(emu, name):
     r, want, tvw, info = sc.gardner_expect(name)
     full, tv, last, status, q = emu.gardner_raw(r["x"], cc.Param(returnTiming=True, **r["p"]))
-    assert not np.any(status) and last.tolist() == info["last_n"]
-    out = full[0:min(max(0, int(np.max(last))), q["Ln"]), :]
-    assert out.shape == want.shape and np.array_equal(out.view(np.uint32), want.view(np.uint32))
-    assert tv.shape == tvw.shape and np.array_equal(tv.view(np.uint64), tvw.view(np.uint64))
-    assert not np.any(full[out.shape[0]:])                      # nothing beyond the furthest output
+    expect = r.get("status", [0] * r["cols"])
+    assert status.tolist() == expect and [int(v) for v, s in zip(last, expect) if not s] == [v for v, s in zip(info["last_n"], expect) if not s]
+    ok = [k for k, s in enumerate(expect) if not s]            # a refused column holds what it had when it was refused
+    assert len(ok) >= 1 and tv.shape == tvw.shape and np.array_equal(tv[:, ok].view(np.uint64), tvw[:, ok].view(np.uint64))
+    rows = sc.reach(r, info)
+    if not any(expect):
+        out = full[0:min(max(0, int(np.max(last))), q["Ln"]), :]
+        assert out.shape == want.shape and np.array_equal(out.view(np.uint32), want.view(np.uint32))
+    else:
+        assert rows <= want.shape[0]
+        assert np.array_equal(np.ascontiguousarray(full[:rows, ok]).view(np.uint32), np.ascontiguousarray(want[:rows, ok]).view(np.uint32))
+    assert not np.any(full[rows:][:, ok])                      # nothing beyond the furthest output
 
 
-def test_clock_drift_rows(emu):
-    """Peaks at the array's ends, a plateau, fewer than two peaks, a negative mean, a mean per column."""
-    t = np.zeros((600, 4))
-    t[100:, 0] += 1.0
-    t[350:, 0] -= 1.0
-    t[500:, 0] += 1.0                                            # three gaps: periods 250 and 150
-    t[2:, 1] -= 1.0
-    t[598:, 1] += 1.0                                            # gaps at the first and the last difference a peak can sit on
-    t[:, 1] -= 5.0
-    t[300:, 2] += 1.0                                            # one gap: nan
-    t[10:, 3] += 0.7
-    t[12:, 3] += 0.7                                             # a plateau of two equal differences apart... and a second peak
-    t[200:, 3] += 0.9
-    for per_column in (0, 1):
-        got = emu.calcClockDrift(t, per_column)
-        want = rs.clock_drift(t) if not per_column else np.array([rs.clock_drift(t[:, k])[0] for k in range(4)])
-        assert np.array_equal(got, want, equal_nan=True), (per_column, got, want)
-    assert np.isnan(emu.calcClockDrift(t)[2]) and np.all(emu.calcClockDrift(t)[[0, 1]] < 0)
-    assert np.array_equal(emu.calcClockDrift(np.zeros(2)), [np.nan], equal_nan=True)
+@pytest.mark.parametrize("name", list(sc.DRIFT_ROWS))
+def test_clock_drift_rows(emu, name):
+    """Peaks owned by chosen lanes and waves, at the array's ends, plateaus, fewer than two peaks, the sign of the mean, a mean per
+    column: tests/clock_shape_cases.py DRIFT_ROWS."""
+    r, t, want, per_column = sc.drift_expect(name)
+    assert np.array_equal(emu.calcClockDrift(t), want, equal_nan=True), (emu.calcClockDrift(t), want)
+    assert np.array_equal(emu.calcClockDrift(t, 1), per_column, equal_nan=True), (emu.calcClockDrift(t, 1), per_column)
+    if name == "mixed600":
+        assert np.isnan(want[2]) and np.all(want[[0, 1]] < 0)
+        assert np.array_equal(emu.calcClockDrift(np.zeros(2)), [np.nan], equal_nan=True)
+
+
+FORMS = dict(real=_lib.CLOCK_REAL, complex=_lib.CLOCK_COMPLEX, components=_lib.CLOCK_COMPONENTS)
+
+
+@pytest.mark.parametrize("name", list(sc.TIMES_ROWS))
+def test_interpolation_at_explicit_times(emu, name):
+    r, x, inFs, outFs, t_re, t_im, want = sc.interp_times_row(name)
+    kw = dict(t_re=np.array(t_re)) if t_im is None else dict(t_re=np.array(t_re), t_im=np.array(t_im))
+    y = emu._interp(np.array(x), inFs, outFs, FORMS[r["form"]], **kw)
+    assert sc.same_bits(y, want), np.argwhere(~(y == want))[:8]
 
 
 @pytest.mark.parametrize("i", range(len(sc.INTERP_ROWS)))
@@ -127,3 +136,7 @@ def test_complex_clip_is_lexicographic(emu):
             want = np.clip(x, -1, 1)
         got = emu.clip(x, -1, 1)
         assert got.dtype == x.dtype and np.array_equal(got, want)
+
+
+def test_the_rows_cover_what_they_claim():
+    sc.check_coverage()
