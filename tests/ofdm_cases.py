@@ -101,6 +101,8 @@ def check_mod(g, got, dtype):
     """A modulator output for the fixture's symbols against the restatement and the reference, at the bounds above; the figures."""
     want = rs.modulate(g["symb"], **kwargs(g))
     peak = np.max(np.abs(want))
+    fr, pre = got.reshape(g["cfg"]["frames"], -1), g["cfg"]["SpS"] * g["cfg"]["G"]
+    assert fr[:, :pre].tobytes() == fr[:, fr.shape[1] - pre:].tobytes()   # the prefix is a copy of the frame's tail
     if np.dtype(dtype) == np.complex128:
         d = rel(got, want)
         assert got.dtype == np.complex128 and d <= TOL_MOD128, d

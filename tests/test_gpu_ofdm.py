@@ -5,8 +5,9 @@ import numpy as np
 import pytest
 
 import ofdm_cases as oc
+import ofdm_shape_cases as sc
 import opticommpy_amd as oa
-from opticommpy_amd import device
+from opticommpy_amd import _lib, device, ofdm
 
 pytestmark = pytest.mark.gpu
 
@@ -80,7 +81,52 @@ def test_calls_that_alternate_between_two_plans():
             oc.check_demod(g, got, H, np.complex128)
 
 
-CLOSED_LOOP_SEED = 5             # see test_closed_loop_on_device_arrays
+def _both_functions(c, route="auto"):
+    """One modulator and one demodulator call for a shape case, each against the restatement."""
+    sc.check_mod(c, oa.modulateOFDM(c.symb, c.param, dtype=np.complex128, _route=route), np.complex128)
+    sc.check_mod(c, oa.modulateOFDM(c.symb, c.param, _route=route), np.complex64)
+    for dtype in (np.complex128, np.complex64):
+        got, H = oa.demodulateOFDM(c.rx.astype(dtype), c.param, _route=route)
+        sc.check_demod(c, got, H, dtype)
+
+
+# two parameter sets the engine's geometry check cannot tell apart: the same Nfft, SpS and G, the same number of pilots and of nulls
+# (hence the same L, Ns, Ni and Np), other carriers.  Only the plan's number says that the tables on the device are the other plan's
+TWIN_A = sc.Row("twin_a", 64, 2, 4, False, (3, 40), (32,), 5)
+TWIN_B = sc.Row("twin_b", 64, 2, 4, False, (10, 55), (20,), 5)
+TWIN_A_NO_PILOTS = sc.Row("twin_a_no_pilots", 64, 2, 4, False, (), (3, 32, 40), 5)
+TWIN_B_NO_PILOTS = sc.Row("twin_b_no_pilots", 64, 2, 4, False, (), (10, 20, 55), 5)
+
+
+@pytest.mark.parametrize("route", ["auto", "rocfft"])
+@pytest.mark.parametrize("twins", [(TWIN_A, TWIN_B), (TWIN_A_NO_PILOTS, TWIN_B_NO_PILOTS)], ids=["pilots", "no_pilots"])
+def test_calls_that_alternate_between_two_plans_of_one_signature(twins, route):
+    """The plans differ in nothing the engine compares but their number: a call that took the tables left on the device for its
+    own would put the pilots and nulls (with pilots: gather the data, draw the lines) at the other plan's carriers."""
+    a, b = (sc.make(r) for r in twins)
+    for c in (a, b):
+        sc.check_conditions(c)
+    (pa, ga), (pb, gb) = ((ofdm._prepare_mod(c.symb, c.param)["plan"], ofdm._prepare_demod(c.rx, c.param)["plan"]) for c in (a, b))
+    assert pa["key"] != pb["key"] and ga["key"] != gb["key"] and len({pa["key"], pb["key"], ga["key"], gb["key"]}) == 4
+    assert all(pa[k] == pb[k] and ga[k] == gb[k] for k in ("Nfft", "Ns", "Ni", "Np")) and pa["SpS"] == pb["SpS"]
+    assert not np.array_equal(pa["src_map"], pb["src_map"]) and not np.array_equal(ga["data"], gb["data"])
+    for _ in range(3):
+        for c in (a, b):
+            _both_functions(c, route)
+
+
+@pytest.mark.parametrize("first", ["auto", "rocfft"])
+def test_calls_that_alternate_between_the_two_routes_on_one_plan(first):
+    """One plan, one number, two tables: register order for the register kernels, natural order around rocFFT."""
+    c = sc.make(TWIN_A)
+    second = "rocfft" if first == "auto" else "auto"
+    assert _lib.ofdm_lds_length(TWIN_A.SpS * TWIN_A.Nfft) and _lib.ofdm_lds_length(TWIN_A.Nfft)
+    for _ in range(3):
+        for route in (first, second):
+            _both_functions(c, route)
+
+
+CLOSED_LOOP_SEED = 5            # see test_closed_loop_on_device_arrays
 
 
 @pytest.mark.parametrize("pilots", [False, True], ids=["no_pilots", "pilots"])

@@ -43,6 +43,36 @@ def test_restated_demodulator_matches_the_reference(name):
     oc.check_demod(g, got.astype(np.complex64), H, np.complex64)
 
 
+def test_the_path_over_an_array_of_frames_is_byte_equal_to_the_loops():
+    """``modulate_frames`` / ``demodulate_frames`` restate the big row (116 600 frames); the loops stay the yardstick, so the two
+    must agree to the byte on every shape row and every fixture, with and without turned frames, in both input types."""
+    import ofdm_shape_cases as sc
+    for row in sc.ROWS:
+        c = sc.make(row)
+        assert row.frames < sc.LOOP_FRAMES                              # c.tx, c.dem and c.H are the loops'
+        assert rs.modulate_frames(c.symb, **c.kwargs).tobytes() == c.tx.tobytes(), row.id
+        assert rs.modulate_frames(c.symb.astype(np.complex64), **c.kwargs).tobytes() == c.tx.tobytes(), row.id
+        for x, (dem, H) in ((c.rx, (c.dem, c.H)), (c.rx.astype(np.complex64), rs.demodulate(c.rx.astype(np.complex64), **c.kwargs))):
+            got, Hg = rs.demodulate_frames(x, **c.kwargs)
+            assert got.tobytes() == dem.tobytes() and np.asarray(Hg).tobytes() == np.asarray(H).tobytes(), row.id
+    for name in oc.CASES:
+        g = oc.load(name)
+        assert rs.modulate_frames(g["symb"], **oc.kwargs(g)).tobytes() == rs.modulate(g["symb"], **oc.kwargs(g)).tobytes()
+        (got, H), (dem, Hw) = rs.demodulate_frames(g["rx"], **oc.kwargs(g)), rs.demodulate(g["rx"], **oc.kwargs(g))
+        assert got.tobytes() == dem.tobytes() and np.asarray(H).tobytes() == np.asarray(Hw).tobytes()
+
+
+def test_every_shape_row_meets_its_conditions():
+    """The conditions of tests/ofdm_shape_cases.py hold on the restatement alone: quadrants, distance from the cut, the mean
+    angle of the alternating rows, the line of the delay rows beyond pi, |H| >= 0.3 -- and the big row is restated by the
+    array path."""
+    import ofdm_shape_cases as sc
+    for row in sc.ROWS + sc.BIG_ROWS:
+        sc.check_conditions(sc.make(row))
+    assert all(r.frames >= sc.LOOP_FRAMES for r in sc.BIG_ROWS)
+    assert {sc.kind(r) for r in sc.EMU_ROWS} == {None, "II", "III", "alternating", "delay"}
+
+
 def test_the_loop_closes_without_a_channel():
     g = oc.load("nb_pilots")
     k = oc.kwargs(g)
