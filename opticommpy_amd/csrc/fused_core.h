@@ -387,22 +387,17 @@ template <typename T> SSF_HD void powers16(cx<T> w, cx<T> *p) {
 // ripple of 1e-3 after BASELINE config 3's 10 010 steps (the reference's own complex64 path, pocketfft with float
 // twiddles, drifts by 5e-4 there).  With the low part the effective factor is exact to 1e-15 and only the random
 // rounding of the products is left, which grows with the square root of the step count.
-#ifndef SSF_C64_HILO
-#define SSF_C64_HILO 1
-#endif
 // v * h for a factor given in double precision
 template <typename T> SSF_HD cx<T> mul_by_d(cx<T> v, cx<double> h) {
     using S = scalar_t<T>;
     if constexpr (sizeof(S) == 8) {
         return v * mk<T>((T)h.re, (T)h.im);
-    } else if constexpr (SSF_C64_HILO) {                                    // float and packed float pairs alike
+    } else {                                                                // float and packed float pairs alike
         const S hr = (S)h.re, hi = (S)h.im;
         const S lr = (S)(h.re - (double)hr), li = (S)(h.im - (double)hi);
         const T cr = fma_s<T>(v.re, lr, -(v.im * splat<T>(li)));            // v.re lr - v.im li
         const T ci = fma_s<T>(v.re, li, v.im * splat<T>(lr));               // v.re li + v.im lr
         return mk<T>(fma_s<T>(v.re, hr, fma_s<T>(-v.im, hi, cr)), fma_s<T>(v.re, hi, fma_s<T>(v.im, hr, ci)));
-    } else {
-        return tmul(v, mk<S>((S)h.re, (S)h.im));
     }
 }
 // ---------------------------------------------------------------------------------------
@@ -422,8 +417,8 @@ template <typename T> SSF_HD tw_entry_t<T> tw_make(cx<double> h) {
         TwEntryF e;
         e.hr = (float)h.re;
         e.hi = (float)h.im;
-        e.lr = SSF_C64_HILO ? (float)(h.re - (double)e.hr) : 0.0f;
-        e.li = SSF_C64_HILO ? (float)(h.im - (double)e.hi) : 0.0f;
+        e.lr = (float)(h.re - (double)e.hr);
+        e.li = (float)(h.im - (double)e.hi);
         return e;
     }
 }
@@ -434,23 +429,19 @@ template <bool CONJ, typename T> SSF_HD cx<T> tw_mul(cx<T> v, const tw_entry_t<T
         return v * mk<T>((T)e.re, CONJ ? (T)-e.im : (T)e.im);
     } else {
         const S hr = e.hr, hi = CONJ ? -e.hi : e.hi, lr = e.lr, li = CONJ ? -e.li : e.li;
-        if constexpr (SSF_C64_HILO) {
-            const T cr = fma_s<T>(v.re, lr, -(v.im * splat<T>(li)));
-            const T ci = fma_s<T>(v.re, li, v.im * splat<T>(lr));
-            return mk<T>(fma_s<T>(v.re, hr, fma_s<T>(-v.im, hi, cr)), fma_s<T>(v.re, hi, fma_s<T>(v.im, hr, ci)));
-        } else {
-            return tmul(v, mk<S>(hr, hi));
-        }
+        const T cr = fma_s<T>(v.re, lr, -(v.im * splat<T>(li)));
+        const T ci = fma_s<T>(v.re, li, v.im * splat<T>(lr));
+        return mk<T>(fma_s<T>(v.re, hr, fma_s<T>(-v.im, hi, cr)), fma_s<T>(v.re, hi, fma_s<T>(v.im, hr, ci)));
     }
 }
 // a real constant given in double precision (radix-3 / 5 butterfly constants of the mixed-radix rows): x * c
 template <typename T> SSF_HD T mul_cd(T x, double c) {
     using S = scalar_t<T>;
     if constexpr (sizeof(S) == 8) return x * (T)c;
-    else if constexpr (SSF_C64_HILO) {
+    else {
         const S hi = (S)c, lo = (S)(c - (double)hi);
         return fma_s<T>(x, hi, x * splat<T>(lo));
-    } else return x * splat<T>((S)c);
+    }
 }
 
 
@@ -531,11 +522,8 @@ SSF_HD int lds_slots_per_fft(int L) { return L + (L >> 4) + 1; }
 // 9 distinct groups for 16 lanes, C = 4 only 7: SQ_LDS_BANK_CONFLICT 2.3 x SQ_ACTIVE_INST_LDS in k_col_pk<10>).
 // Measured (same box, A/B): C = 4 (packed pairs, columns of 1024) column launch 62.0 -> 61.0 us, +1 % steps/s at config 3;
 // C = 8 (complex128 Manakov) no gain within the noise (5 768 vs 5 672 steps/s the other way): applied to C <= 4 only.
-#ifndef SSF_COLPAD
-#define SSF_COLPAD 1
-#endif
 SSF_HD int lds_col_stride(int L, int C, int elem_bytes) {
-    if (!SSF_COLPAD || elem_bytes != 16 || C > 4 || C < 2) return lds_slots_per_fft(L);
+    if (elem_bytes != 16 || C > 4 || C < 2) return lds_slots_per_fft(L);
     const int want = 16 / C, s = L + (L >> 4);
     return s + ((want - s) & 15);
 }

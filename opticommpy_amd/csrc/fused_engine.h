@@ -399,7 +399,7 @@ template <typename T, class Backend> class FusedCore {
             row_block = fpw * tpf2;
             row_grid = (int)(nfft / fpw);
             row_lds = std::max((size_t)fpw * lds_slots_per_fft(1 << sp.l2) * sizeof(C), (size_t)row_block * 16 + 2048);
-            if ((SSF_TW_TAB & 1) && sizeof(S) == 4) {          // single precision: the workgroup's twiddle table behind the transform
+            if (sizeof(S) == 4) {                              // single precision: the workgroup's twiddle table behind the transform
                 row_tw_off = (int)((row_lds + 15) / 16 * 16);  // area (fused_kernels.h: TwSrc; double precision and the column
                 row_lds = (size_t)row_tw_off + kTwLdsBytes;    // stages are faster without: profiles/r4_ab_twiddle_tables.txt)
             }
@@ -660,7 +660,7 @@ template <typename T, class Backend> class FusedCore {
                         pgrid = std::max(prow, pcol);
                         plds = std::max((size_t)fpw * lds_slots_per_fft(1 << sp.l2), (size_t)Cc * lds_col_stride(1 << sp.l1, Cc, (int)sizeof(C))) * sizeof(C);
                         plds = std::max(plds, (size_t)256 * 16 + 2048);
-                        if ((SSF_TW_TAB & 1) && sizeof(S) == 4) {       // the row stage's twiddle table (single precision)
+                        if (sizeof(S) == 4) {                           // the row stage's twiddle table (single precision)
                             ptw = (int)((plds + 15) / 16 * 16);
                             plds = (size_t)ptw + kTwLdsBytes;
                         }

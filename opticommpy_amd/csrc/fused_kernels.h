@@ -171,10 +171,10 @@ template <int R> SSF_HD void tw_powers(cx<double> w1, cx<double> *p) {
 //  * Generated in registers (the default): one sincospi per pass for the base w = cis(2 pi j / L_i) + a double-precision
 //    power tree of depth <= 4, rounded once.  The library sincospi is ~100 issue slots (a Horner scheme whose 24
 //    coefficients are moved into registers one by one), as much as the tree and the fifteen products it feeds, and a
-//    kernel's forward and inverse transforms use conjugate bases: SSF_TW_REUSE keeps the bases of the first transform (4
+//    kernel's forward and inverse transforms use conjugate bases: the bases of the first transform are kept (4
 //    registers per pass; j is the same for every butterfly a thread carries in a pass >= 1, and in pass 0 there is one)
 //    and the second one conjugates them -- half the sincospi calls of a launch.
-//  * SSF_TW_TAB bit 0: the next-to-last pass (pass 0 of a two-pass transform, pass 1 of a three-pass one) reads its factors
+//  * From a table: the next-to-last pass (pass 0 of a two-pass transform, pass 1 of a three-pass one) reads its factors
 //    from a table in LDS that the workgroup builds when it starts (fused_core.h: tw_entry_t; j < r_last, s < r: at most 256
 //    entries = 4 KiB).  Measured (profiles/r4_ab_twiddle_tables.txt, same box): it pays only where a factor is expensive to
 //    make -- the hi + lo float quadruples of the single-precision rows (row launch 49.2 -> 47.2 us at config 3) -- and costs
@@ -182,16 +182,10 @@ template <int R> SSF_HD void tw_powers(cx<double> w1, cx<double> *p) {
 //    60.8 -> 62.1 us.  The host therefore offers the table (tw_off > 0) to the single-precision row stage only.  A second
 //    table for pass 0 of three-pass transforms in global memory (L2-resident, 64 KiB) gained nothing on top (rows 47.6 us)
 //    and cost double precision another 1.3 us per row launch: removed again.
-#ifndef SSF_TW_TAB
-#define SSF_TW_TAB 1
-#endif
-#ifndef SSF_TW_REUSE
-#define SSF_TW_REUSE 1
-#endif
 constexpr int kTwMaxPass = 5;
 template <typename T> struct TwSrc {
     const tw_entry_t<T> *lds = nullptr;      // table of pass npass - 2: entry [s * r_last + j]
-    cx<double> base[kTwMaxPass];             // SSF_TW_REUSE: cis(+2 pi j / L_i) of the passes generated so far
+    cx<double> base[kTwMaxPass];             // kept bases: cis(+2 pi j / L_i) of the passes generated so far
     bool have[kTwMaxPass] = {false, false, false, false, false};
 };
 constexpr int kTwLdsBytes = 4096;
@@ -199,7 +193,7 @@ constexpr int kTwLdsBytes = 4096;
 // the workgroup's LDS table (no barrier inside: the caller's next barrier -- the first exchange of a three-pass transform, an
 // explicit one for two passes -- publishes it)
 template <typename T, class Ctx> SSF_HD void tw_lds_build(Ctx &ctx, const PassPlan &p, tw_entry_t<T> *tab) {
-    if (!(SSF_TW_TAB & 1) || p.npass < 2) return;
+    if (p.npass < 2) return;
     const int it = p.npass - 2, lgr = p.lg(it), lgl = p.lg(p.npass - 1);
     for (int t = ctx.tid; t < (1 << (lgr + lgl)); t += ctx.nthreads) {
         const int s = t >> lgl, j = t & ((1 << lgl) - 1);
@@ -221,7 +215,7 @@ SSF_HD void apply_tw(const PassPlan &p, int i, int bb, cx<T> *v, TwSrc<T> &src, 
         return;
     }
     cx<double> w1;
-    const bool keep = SSF_TW_REUSE && i < kTwMaxPass && (first || i > 0);      // (pass >= 1: every butterfly of the thread has this j)
+    const bool keep = i < kTwMaxPass && (first || i > 0);      // (pass >= 1: every butterfly of the thread has this j)
     if (keep && src.have[i]) {
         w1 = SIGN > 0 ? src.base[i] : conj(src.base[i]);
     } else {
@@ -506,8 +500,8 @@ template <typename T> SSF_HD long long row_n1(const RowArgs<T> &a) { return a.N1
 
 // linear operator for the V registers of a last-radix-V butterfly (V = 16 | 8): bins k0 + (N/V) q, signed q' = q or q - V;
 // phase cth (k0 + dk q')^2 = A * B^q' * C_|q'| with C_m = cis(cth dk^2 m^2) = the control block's table at 16/V * m
-// (the two sines / cosines of it by themselves: they depend on the thread's bins only, not on the data, so the row stage
-//  evaluates them while its row is still in flight -- SSF_EARLY_BASES)
+// (the two sines / cosines of it by themselves: they depend on the thread's bins only, not on the data, so the paired row stage
+//  makes them once for both of its rounds)
 struct Lin16Bases {
     cx<double> A, B1;       // A: the unit phasor cis(cth k0^2) (the magnitude is applied with the operator), B1 = cis(2 cth k0 dk)
     double cth;             // the operator constant they were made for
@@ -568,13 +562,9 @@ SSF_HD cx<double> lin_at(const LinOp &lo, long long k, int log2N) {
 // -- 3.5 us that the lead workgroup finishes late, a quarter of a launch at small N (round 2: groups of eight).  Round 5: the 38
 // words of the block were still four groups and six single words = ten dependent round trips in front of the lead workgroup's own
 // work, in EVERY launch (the generated code shows a load + s_waitcnt vmcnt(0) + store per word of the tail); now one round trip.
-#ifndef SSF_CTRL_WIDE
-#define SSF_CTRL_WIDE 1
-#endif
 SSF_HD void ctrl_forward(const Ctrl *cin, Ctrl *cout, int nwords) {
     const unsigned long long *src = (const unsigned long long *)cin;
     unsigned long long *dst = (unsigned long long *)cout;
-#if SSF_CTRL_WIDE
     constexpr int kMax = (int)(sizeof(Ctrl) / 8);
     unsigned long long w[kMax];
 #pragma unroll
@@ -583,17 +573,6 @@ SSF_HD void ctrl_forward(const Ctrl *cin, Ctrl *cout, int nwords) {
 #pragma unroll
     for (int q = 0; q < kMax; ++q)
         if (q < nwords) dst[q] = w[q];
-#else
-    int i = 0;
-    for (; i + 8 <= nwords; i += 8) {
-        unsigned long long w[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) w[q] = src[i + q];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) dst[i + q] = w[q];
-    }
-    for (; i < nwords; ++i) dst[i] = src[i];
-#endif
 }
 
 // a value that is the same in every lane, as a scalar (device code)
@@ -764,12 +743,6 @@ template <typename T, class Ctx> SSF_HD void row_mixed_body(Ctx &ctx, const RowA
     const cx<T> *gin = a.src ? a.src + rr * L : g;
     LinOp lo;
     double part[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-#if SSF_EARLY_BASES
-    // the operator constant as the previous launch left it (a scalar load, ahead of everything: the vector loads of the whole
-    // operator inside row_ctrl queue up behind the row): the thread's operator bases are made from it while the row is in flight,
-    // and made again in the (rare) launch that derives a new operator
-    const double cth_pre = a.use_ctrl ? a.cin->lin.cth : (a.lin ? a.lin->cth : 0.0);
-#endif
     if (a.use_ctrl) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -791,7 +764,7 @@ template <typename T, class Ctx> SSF_HD void row_mixed_body(Ctx &ctx, const RowA
     // a launch at rows of 3750: one read-modify-write per bin, each waiting for the one before it.)
     MixRowOp op;
     // The row is staged into LDS with the control logic behind its loads, and goes from the last pass's butterflies straight back to
-    // global memory (mix_dif_op_dit; SSF_MIX_IO).
+    // global memory (mix_dif_op_dit).
     auto ctrl = [&]() {
         if (a.use_ctrl) {
             ctx.issue_fence();
@@ -829,35 +802,9 @@ template <typename T, class Ctx> SSF_HD void row_mixed_body(Ctx &ctx, const RowA
 // them by inline assembly, which the hazard recogniser does not look into: where the data sat in a temporary register tuple
 // that the next value's moves overwrote at once -- the packed complex64 kernel -- the store sent the NEXT element's data
 // (rel-L2 0.67 at every size); the double-precision kernel's values happened to live in aligned tuples of their own and
-// passed every test.  SSF_WT_ROWS: bit 0 double, bit 1 packed pairs, bit 2 float.  Round 4, compiler-visible stores, same box
-// (profiles/r4_ab_twiddle_tables.txt): double 24.1 -> 22.5 us per row launch, packed pairs 47.7 -> 45.5 us with correct results.
-#ifndef SSF_WT_ROWS
-#define SSF_WT_ROWS 3
-#endif
-#ifndef SSF_LOAD_ORDER
-#define SSF_LOAD_ORDER 1      // loads of a row in the order its first butterfly consumes them: + 0.5 ... 1.3 %, 8 of 8 (profiles/r5_ab_load_order.txt)
-#endif
-#ifndef SSF_EARLY_BASES
-#define SSF_EARLY_BASES 0
-#endif
-#ifndef SSF_SPEC_G
-#define SSF_SPEC_G 0
-#endif
-// Experiments of round 6 on the double-precision Manakov column stage (appendix #48, #49):
-//  SSF_PAIR_DPP   the x / y partner threads of a sample sit in NEIGHBOURING lanes (pol = tid & 1) and swap powers, rotations and
-//                 |d rot|^2 with DPP moves (ctx.xchg) instead of through LDS: no LDS traffic and no barrier for the pair exchange
-//  SSF_THETA_F32  the phase array of the latest rotation is kept in single precision: it only enters the convergence measure
-//                 (4 sin^2((theta_new - theta_old) / 2), relative error ~1e-8 of lim), never the field -- 4 instead of 8 bytes
-//                 read and written per sample and iteration
-#ifndef SSF_PAIR_DPP
-#define SSF_PAIR_DPP 0
-#endif
-#ifndef SSF_THETA_F32
-#define SSF_THETA_F32 0
-#endif
-template <typename T> constexpr bool wt_rows() {
-    return sizeof(scalar_t<T>) == 8 ? (SSF_WT_ROWS & 1) != 0 : sizeof(T) == 8 ? (SSF_WT_ROWS & 2) != 0 : (SSF_WT_ROWS & 4) != 0;
-}
+// passed every test.  Written through in double precision and in packed pairs, not in plain float.  Round 4, compiler-visible stores,
+// same box (profiles/r4_ab_twiddle_tables.txt): double 24.1 -> 22.5 us per row launch, packed pairs 47.7 -> 45.5 us with correct results.
+template <typename T> constexpr bool wt_rows() { return sizeof(scalar_t<T>) == 8 || sizeof(T) == 8; }
 template <int V, typename T, class Ctx>
 SSF_HD void row_store(Ctx &ctx, const RowArgs<T> &a, cx<T> *G, const PassPlan &p, int f, int b, const cx<T> *v) {
     const int fpw = ctx.nthreads / p.tpf;
@@ -948,12 +895,6 @@ template <typename T, int LG, int V = 16, class Ctx> SSF_HD void row_body(Ctx &c
     // makes the decision wait for the row: +2.5 us per launch.  Starting half of the workgroups
     // late, so that co-resident workgroups are out of phase, was measured and does not help.)
     double part[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-#if SSF_EARLY_BASES
-    // the operator constant as the previous launch left it (a scalar load, ahead of everything: the vector loads of the whole
-    // operator inside row_ctrl queue up behind the row): the thread's operator bases are made from it while the row is in flight,
-    // and made again in the (rare) launch that derives a new operator
-    const double cth_pre = a.use_ctrl ? a.cin->lin.cth : (a.lin ? a.lin->cth : 0.0);
-#endif
     if (a.use_ctrl) {
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -967,10 +908,9 @@ template <typename T, int LG, int V = 16, class Ctx> SSF_HD void row_body(Ctx &c
         }
         ctx.issue_fence();
     }
-#if SSF_LOAD_ORDER
-    // Experiment (appendix #43): the row's loads issued in the order the first butterfly consumes them (bit-reversed: dft16 starts
-    // with v[0] + v[8], v[4] + v[12], ...), in groups the scheduler may not merge, so that the waits can be per group and the first
-    // additions start while the rest of the row is still in flight.
+    // The row's loads are issued in the order the first butterfly consumes them (bit-reversed: dft16 starts with v[0] + v[8],
+    // v[4] + v[12], ...), in groups the scheduler may not merge, so that the waits can be per group and the first additions start
+    // while the rest of the row is still in flight: + 0.5 ... 1.3 %, 8 of 8 (appendix #43, profiles/r5_ab_load_order.txt).
     {
         constexpr int ord16[16] = {0, 8, 4, 12, 2, 10, 6, 14, 1, 9, 5, 13, 3, 11, 7, 15};
         constexpr int ord8[8] = {0, 4, 2, 6, 1, 5, 3, 7};
@@ -981,20 +921,15 @@ template <typename T, int LG, int V = 16, class Ctx> SSF_HD void row_body(Ctx &c
             if ((i & 3) == 3) ctx.issue_fence();
         }
     }
-#else
-#pragma unroll
-    for (int q = 0; q < V; ++q) v[q] = g[b + p.tpf * q];
-#endif
     // single precision: the next-to-last pass takes its hi + lo factors from a table in LDS, built while the row is in flight (TwSrc)
-    constexpr bool kTab = (SSF_TW_TAB & 1) && sizeof(scalar_t<T>) == 4;
+    constexpr bool kTab = sizeof(scalar_t<T>) == 4;
     tw_entry_t<T> *tab = nullptr;
     if (kTab) {
         tab = (tw_entry_t<T> *)(ctx.lds + a.tw_off);
         tw_lds_build<T>(ctx, p, tab);
     }
     // the paired row stage (the note at Ctrl::last_nit) exists in the 16-value double-precision kernels only
-    // (not with SSF_SPEC_G, whose column stages fetch G before they know where their spectrum is)
-    constexpr bool kPair = !SSF_SPEC_G && V == 16 && sizeof(T) == 8 && sizeof(scalar_t<T>) == 8 && pair_row_length(LG);
+    constexpr bool kPair = V == 16 && sizeof(T) == 8 && sizeof(scalar_t<T>) == 8 && pair_row_length(LG);
     RowPair rp;
     if (a.use_ctrl) {
         ctx.issue_fence();
@@ -1027,7 +962,7 @@ template <typename T, int LG, int V = 16, class Ctx> SSF_HD void row_body(Ctx &c
     if constexpr (kPair) {
 #pragma unroll
         for (int i = 0; i < kTwMaxPass; ++i) {
-            if (SSF_TW_REUSE && i < p.npass && p.lgLn(i) > 0) {
+            if (i < p.npass && p.lgLn(i) > 0) {
                 twp.base[i] = tw_base(+1, pass_j(p, i, b), pass_lgLi(p, i));
                 twp.have[i] = true;
             }
@@ -1059,24 +994,6 @@ template <typename T, int LG, int V = 16, class Ctx> SSF_HD void row_body(Ctx &c
             lbr.cth = lbp.cth;
         }
         if (a.prio) ctx.template setprio<2>();
-#if SSF_EARLY_BASES
-        // Everything that depends on the thread's position only -- the twiddle bases of all passes (one sincospi each; the inverse
-        // transform conjugates them) and the two sines / cosines of the linear operator -- is evaluated HERE, while the row is still
-        // in flight and the VALU has nothing else to do (appendix #44).
-        Lin16Bases lb{};
-        const bool lin16 = (a.use_ctrl || a.lin) && p.lg(last) == lgV;
-        {
-#pragma unroll
-            for (int i = 0; i < kTwMaxPass; ++i) {
-                if (i < p.npass && p.lgLn(i) > 0 && !(kTab && i == p.npass - 2)) {
-                    tws.base[i] = tw_base(+1, pass_j(p, i, br), pass_lgLi(p, i));
-                    tws.have[i] = true;
-                }
-            }
-            if (lin16) lb = lin16_bases<V>(cth_pre, k1r + ((long long)rev_pos(p, reg_pos(p, last, br, 0)) << a.log2N1), log2N);
-            ctx.issue_fence();
-        }
-#endif
         fft_dif<-1, V, kTab>(ctx, p, br, v, l, tws);
         ctx.mark(2);
         if (a.prio) ctx.template setprio<1>();
@@ -1091,16 +1008,11 @@ template <typename T, int LG, int V = 16, class Ctx> SSF_HD void row_body(Ctx &c
 #pragma unroll
             for (int idx = 0; idx < V; ++idx) v[idx] = v[idx] * h[reg_pos(p, last, br, idx)];
         } else if (p.lg(last) == lgV) {
-#if SSF_EARLY_BASES
-            if (lo.cth != lb.cth) lb = lin16_bases<V>(lo.cth, k1r + ((long long)rev_pos(p, reg_pos(p, last, br, 0)) << a.log2N1), log2N);
-            apply_lin16<V>(lo, lb, v);
-#else
             if constexpr (kPair) apply_lin16<V>(lo, lbr, v);
             else {
                 const long long k0 = k1r + ((long long)rev_pos(p, reg_pos(p, last, br, 0)) << a.log2N1);
                 apply_lin16<V>(lo, k0, log2N, v);
             }
-#endif
         } else {
 #pragma unroll
             for (int idx = 0; idx < V; ++idx) {
@@ -1220,8 +1132,6 @@ template <typename T> SSF_HD ColArgs<T> unit_view(const ColArgs<T> &a, int u) {
 // only partly filled, and its surplus threads (valid == false) load zeros and store nothing.
 template <typename T, int LG, class Ctx, bool RAGGED = false, int V = 16> struct ColGeom {
     static constexpr int kV = V;
-    static constexpr bool kDppT = SSF_PAIR_DPP && V == 16 && sizeof(T) == 8;    // (the polarisation-split double-precision kernels)
-    bool dpp;                 // the partner thread is the neighbouring lane (Manakov stage only)
     PassPlan p;
     int half, pol, t, C, c, b, n2, N2;
     bool valid;
@@ -1231,14 +1141,8 @@ template <typename T, int LG, class Ctx, bool RAGGED = false, int V = 16> struct
     SSF_HD ColGeom(Ctx &ctx, const ColArgs<T> &a) {
         p = make_plan(LG > 0 ? LG : a.log2N1, V == 16 ? 4 : 3);
         half = ctx.nthreads / a.npol;
-        dpp = kDppT && a.npol == 2;
-        if (kDppT && a.npol == 2) {
-            pol = ctx.tid & 1;
-            t = ctx.tid >> 1;
-        } else {
-            pol = ctx.tid / half;
-            t = ctx.tid - pol * half;
-        }
+        pol = ctx.tid / half;
+        t = ctx.tid - pol * half;
         C = half / p.tpf;
         c = t % C;
         b = t / C;
@@ -1288,11 +1192,11 @@ template <typename T, int LG, class Ctx, bool RAGGED = false, int V = 16> struct
 // register q holds k1 = b + tpf*q of column n2  ->  v[q] *= cis(SIGN * 2 pi n2 k1 / N)
 struct GTw {                      // the two bases of a thread's inter-pass twiddles, cis(+2 pi n2 b / N) and cis(+2 pi n2 tpf / N)
     cx<double> w0, ws;
-    bool have = false;            // SSF_TW_REUSE: the inverse transform's bases are kept, the forward one conjugates them
+    bool have = false;            // the inverse transform's bases are kept, the forward one conjugates them
 };
 template <int SIGN, bool RAGGED, typename T, class G> SSF_HD void global_twiddle(const G &g, int log2N, cx<T> *v, GTw &gt) {
     cx<double> w0, ws;
-    if (SSF_TW_REUSE && gt.have) {
+    if (gt.have) {
         w0 = SIGN > 0 ? gt.w0 : conj(gt.w0);
         ws = SIGN > 0 ? gt.ws : conj(gt.ws);
     } else {
@@ -1304,11 +1208,9 @@ template <int SIGN, bool RAGGED, typename T, class G> SSF_HD void global_twiddle
             w0 = cis2pi<double>((double)SIGN * scale_pow2((double)(((long long)g.n2 * g.b) & (N - 1)), log2N));
             ws = cis2pi<double>((double)SIGN * scale_pow2((double)(((long long)g.n2 * g.p.tpf) & (N - 1)), log2N));
         }
-        if (SSF_TW_REUSE) {
-            gt.w0 = SIGN > 0 ? w0 : conj(w0);
-            gt.ws = SIGN > 0 ? ws : conj(ws);
-            gt.have = true;
-        }
+        gt.w0 = SIGN > 0 ? w0 : conj(w0);
+        gt.ws = SIGN > 0 ? ws : conj(ws);
+        gt.have = true;
     }
     // t[q] = w0 * ws^q by doubling: ws^2, ws^4, ws^8, then t[q + 2^k] = t[q] * ws^(2^k) -- 18 complex products of depth <= 7
     // (a power tree of ws followed by w0 * ws^q costs 30); rounded once, where it is applied (see tw_powers)
@@ -1335,13 +1237,6 @@ template <int SIGN, bool RAGGED, typename T, class G> SSF_HD void global_twiddle
 // The caller guarantees (barrier) that `sh` is free on entry.
 template <typename U, class Ctx, class G> SSF_HD void pair_swap(Ctx &ctx, const G &g, const U *mine, U *other, U *sh) {
     constexpr int V = G::kV;
-    if constexpr (G::kDppT) {
-        if (g.dpp) {
-#pragma unroll
-            for (int idx = 0; idx < V; ++idx) other[idx] = (U)ctx.xchg((double)mine[idx]);
-            return;
-        }
-    }
 #pragma unroll
     for (int idx = 0; idx < V; ++idx) sh[(size_t)(g.pol * V + idx) * g.half + g.t] = mine[idx];
     ctx.sync();
@@ -1369,18 +1264,6 @@ template <typename T, class Ctx, class G>
 SSF_HD void pair_cis(Ctx &ctx, const G &g, const T *ang_own, cx<T> *rot, cx<T> *sh) {
     constexpr int V = G::kV, H = V / 2;
     cx<T> own[H], oth[H];
-    if constexpr (G::kDppT) {
-        if (g.dpp) {
-#pragma unroll
-            for (int j = 0; j < H; ++j) {
-                own[j] = cis_t<T>(ang_own[j]);
-                oth[j] = mk<T>((T)ctx.xchg((double)own[j].re), (T)ctx.xchg((double)own[j].im));
-            }
-#pragma unroll
-            for (int idx = 0; idx < V; ++idx) rot[idx] = pick16(g, idx, own, oth);
-            return;
-        }
-    }
 #pragma unroll
     for (int j = 0; j < H; ++j) {
         own[j] = cis_t<T>(ang_own[j]);
@@ -1417,7 +1300,7 @@ SSF_HD void mk_step_start(Ctx &ctx, const G &g, const ColArgs<T> &a, const cx<T>
     T mine[V], oth[V];
 #pragma unroll
     for (int idx = 0; idx < V; ++idx) mine[idx] = norm2_pinned(v[idx]);
-    if (lds_busy && !(G::kDppT && g.dpp)) ctx.sync();
+    if (lds_busy) ctx.sync();
     pair_swap(ctx, g, mine, oth, shT);
     const T c8g = (T)a.k.c8g;
     double m = -INFINITY;
@@ -1437,63 +1320,6 @@ SSF_HD void mk_step_start(Ctx &ctx, const G &g, const ColArgs<T> &a, const cx<T>
         if (ctx.tid == 0) a.pmax[ctx.bid] = m;
     }
     ctx.sync();                                  // scratch reads done before the FFT reuses the LDS
-}
-// the phase array of the latest rotation (see SSF_THETA_F32)
-template <typename T, class G> SSF_HD T theta_ld(const G &g, const T *th, long long i) {
-    if constexpr (SSF_THETA_F32 && sizeof(T) == 8) return (T)g.ld((const float *)th, i);
-    else return g.ld(th, i);
-}
-template <typename T, class G> SSF_HD void theta_st(const G &g, T *th, long long i, T x) {
-    if constexpr (SSF_THETA_F32 && sizeof(T) == 8) g.st((float *)th, i, (float)x);
-    else g.st(th, i, x);
-}
-// mk_advance with the partner in the neighbouring lane (SSF_PAIR_DPP): the same arithmetic, every exchange a DPP move -- no LDS, no
-// barrier; rotation and |d rot|^2 of a sample are applied as soon as its owner has them
-template <typename T, class Ctx, class G>
-SSF_HD void mk_advance_dpp(Ctx &ctx, const G &g, const ColArgs<T> &a, cx<T> *v, const T *Pbuf, T shz, bool first,
-                           double &num, double &den, double &pch_sum) {
-    constexpr int V = G::kV, H = V / 2;
-    T pw8[H], prev8[H], ang8[H];
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const long long t = own_time_off(g, j);
-        pw8[j] = g.ld(Pbuf, g.pbase + t);
-        prev8[j] = first ? (T)0 : theta_ld(g, a.Theta, g.pbase + t);
-    }
-    const T c8g = (T)a.k.c8g;
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const T lo = norm2(v[j]), hi = norm2(v[j + H]);
-        const T nown = g.pol ? hi : lo, noth = g.pol ? lo : hi;
-        const T po = (T)ctx.xchg((double)noth);                  // the partner's power of the sample I own
-        const T ax = g.pol ? po : nown, ay = g.pol ? nown : po;
-        const T pw = pw8[j];
-        pch_sum += (double)pw;
-        ang8[j] = shz * (c8g * (pw + ax + ay) / (T)2);
-        if (first) prev8[j] = shz * (c8g * (pw + pw) / (T)2);
-    }
-    ctx.mark(6);
-#pragma unroll
-    for (int idx = 0; idx < V; ++idx) v[idx] = g.ld(a.Ehd, g.rowbase + g.time_off(idx));
-    ctx.mark(7);
-#pragma unroll
-    for (int j = 0; j < H; ++j) {
-        const T ang = ang8[j];
-        const double s = sin_half_angle((double)ang - (double)prev8[j]);
-        theta_st(g, a.Theta, g.pbase + own_time_off(g, j), ang);
-        const cx<T> ro = cis_t<T>(ang);
-        const T dd = (T)(4.0 * s * s);
-        const cx<T> rp = mk<T>((T)ctx.xchg((double)ro.re), (T)ctx.xchg((double)ro.im));
-        const T dp = (T)ctx.xchg((double)dd);
-        // register j is owned by the x thread, register j + H by the y thread
-        const cx<T> r_lo = g.pol ? rp : ro, r_hi = g.pol ? ro : rp;
-        const T d_lo = g.pol ? dp : dd, d_hi = g.pol ? dd : dp;
-        const double w0 = (double)norm2(v[j]), w1 = (double)norm2(v[j + H]);
-        num += w0 * (double)d_lo + w1 * (double)d_hi;
-        den += w0 + w1;
-        v[j] = v[j] * r_lo;
-        v[j + H] = v[j + H] * r_hi;
-    }
 }
 // next iterate (channels.py:436, 414-417): v holds E_fd(it) on entry and E_hd * rot_{it+1} on exit;
 // accumulates the sums of lim_{it+1} = |E_hd (rot_{it+1} - rot_it)| / |E_hd| (see the header note).
@@ -1515,7 +1341,7 @@ SSF_HD void mk_advance(Ctx &ctx, const G &g, const ColArgs<T> &a, cx<T> *v, cons
     for (int j = 0; j < H; ++j) {
         const long long t = own_time_off(g, j);
         pw8[j] = g.ld(Pbuf, g.pbase + t);
-        prev8[j] = first ? (T)0 : theta_ld(g, a.Theta, g.pbase + t);
+        prev8[j] = first ? (T)0 : g.ld(a.Theta, g.pbase + t);
     }
 #pragma unroll
     for (int j = 0; j < H; ++j) {
@@ -1551,7 +1377,7 @@ SSF_HD void mk_advance(Ctx &ctx, const G &g, const ColArgs<T> &a, cx<T> *v, cons
         const T ang = ang8[j], prev = prev8[j];
         // |rot_new - rot_old|^2 = 4 sin^2((theta_new - theta_old) / 2)
         const double s = sin_half_angle((double)ang - (double)prev);
-        theta_st(g, a.Theta, g.pbase + t, ang);                   // read and written by the owner only
+        g.st(a.Theta, g.pbase + t, ang);                   // read and written by the owner only
         shC[(size_t)own_idx(g, j) * g.half + g.t] = cis_t<T>(ang);
         shD[(size_t)own_idx(g, j) * g.half + g.t] = (T)(4.0 * s * s);
     }
@@ -1732,8 +1558,6 @@ template <class Ctx, class Args> SSF_HD void mk_col_stage(Ctx &ctx, const Args &
     }
 }
 
-// (the DPP variant only exists where the geometry can have it: a run-time test of a compile-time false costs nothing)
-#define G_DPP(g) (std::remove_reference<decltype(g)>::type::kDppT && (g).dpp)
 // MODE is one of CM_*; the Manakov mode picks its stage from the Ctrl state.
 // CI > 0: the workgroup's CI columns (per polarisation row) are interleaved in LDS (lds_put); the launch must have exactly CI of them.
 // SG: the stage groups this instantiation carries (Manakov mode; see stage_group).
@@ -1756,7 +1580,7 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
     // This instantiation forwards the control block through vector registers (MkColStage::chain_kernel): fetched by scalar
     // loads its 76 words sit in scalar registers next to the uniform values of two stages, and twelve of those were spilled
     // into lanes of a vector register; at the top of the kernel the vector registers are free.
-    constexpr bool kChain = kMk && SG == (SG_H | SG_RARE) && V == 16 && sizeof(T) == 8 && !RAGGED && CI == 0 && !SSF_SPEC_G;
+    constexpr bool kChain = kMk && SG == (SG_H | SG_RARE) && V == 16 && sizeof(T) == 8 && !RAGGED && CI == 0;
     // ---- what does this launch do? ------------------------------------------------------
     bool do_inv = false, do_fwd = false;
     int op = -1;     // Manakov: 0 = S (span start), 1 = H, 2 = I, 3 = rebuild iterate 0
@@ -1767,19 +1591,6 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
     ctx.mark(0);
     ColGeom<T, LG, Ctx, RAGGED, V> g(ctx, a);
     cx<T> v[V];
-#if SSF_SPEC_G
-    // The spectrum is fetched BEFORE the control block is looked at (its addresses do not depend on the state): the block was
-    // written by the previous launch on another XCD, so its first read at the start of a launch is a miss that 512 workgroups
-    // wait for before they know their stage -- one memory latency in front of every column launch's loads.  A launch that
-    // turns out to have nothing to do (or a rare stage that starts from the time-domain field) drops the values.
-    if (kMk) {
-#pragma unroll
-        for (int q = 0; q < V; ++q) {
-            v[q] = g.ld(a.G, g.rowbase + g.freq_off(q));
-            if ((q & 3) == 3) ctx.issue_fence();
-        }
-    }
-#endif
     if (kMk) {
         MkColStage st;
         if constexpr (kChain) {
@@ -1843,9 +1654,7 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
 #pragma unroll
             for (int q = 0; q < V; ++q) {
                 v[q] = g.ld(Gin, g.rowbase + g.freq_off(q));
-#if SSF_LOAD_ORDER
                 if ((q & 3) == 3) ctx.issue_fence();
-#endif
             }
             cx<T> e[V];
             if (c.it == 0 && !exact0 && lim0_bound_sample<V>(0, g.b)) e[0] = g.ld(Tcur, g.rowbase + g.time_off(0));
@@ -1909,23 +1718,19 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
     GTw gtw;
     cx<T> e_pre{};
     if (do_inv) {
-        if (!(kMk && SSF_SPEC_G)) {
-            auto load_spectrum = [&](const cx<T> *Gin) {
+        auto load_spectrum = [&](const cx<T> *Gin) {
 #pragma unroll
-                for (int q = 0; q < V; ++q) {
-                    v[q] = g.ld(Gin, g.rowbase + g.freq_off(q));
-#if SSF_LOAD_ORDER
-                    if ((q & 3) == 3) ctx.issue_fence();     // (appendix #43: the inter-pass twiddles are applied in this order, group by group)
-#endif
-                }
-            };
-            // (after a paired row stage the final stage finds its spectrum in the buffer it is about to fill: same tile, loaded first.
-            //  In place only because every thread's loads are consumed before the first exchange barrier of the inverse transform and
-            //  the stores come behind it: the transform needs two passes or more -- columns of 32 up with 16 values per thread -- or one
-            //  thread per column, which holds for every column length that can pair.  The emulator's workgroups cannot show a violation.)
-            if constexpr (kMk && kgFIN) load_spectrum(paired ? Tnew : a.G);
-            else load_spectrum(a.G);
-        }
+            for (int q = 0; q < V; ++q) {
+                v[q] = g.ld(Gin, g.rowbase + g.freq_off(q));
+                if ((q & 3) == 3) ctx.issue_fence();     // (appendix #43: the inter-pass twiddles are applied in this order, group by group)
+            }
+        };
+        // (after a paired row stage the final stage finds its spectrum in the buffer it is about to fill: same tile, loaded first.
+        //  In place only because every thread's loads are consumed before the first exchange barrier of the inverse transform and
+        //  the stores come behind it: the transform needs two passes or more -- columns of 32 up with 16 values per thread -- or one
+        //  thread per column, which holds for every column length that can pair.  The emulator's workgroups cannot show a violation.)
+        if constexpr (kMk && kgFIN) load_spectrum(paired ? Tnew : a.G);
+        else load_spectrum(a.G);
         // the one sample per thread that the bound of lim_0 compares with the field at the step start: fetched here, behind the
         // spectrum, instead of where it is used -- there the load was issued and waited for on the spot (s_waitcnt vmcnt(0) right
         // behind it: a whole memory round trip exposed in the middle of the first iterate's launch of every step)
@@ -1973,7 +1778,7 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
                 }
             }
             cx<T> rot[V];
-            if (!G_DPP(g)) ctx.sync();               // inverse transform's LDS reads are done
+            ctx.sync();                              // inverse transform's LDS reads are done
             pair_cis(ctx, g, ang, rot, shC);
 #pragma unroll
             for (int idx = 0; idx < V; ++idx) v[idx] = v[idx] * rot[idx];
@@ -2002,8 +1807,7 @@ SSF_HD void col_body(Ctx &ctx, const ColArgs<T> &a) {
                 for (int idx = 0; idx < V; ++idx)
                     if (!sparse || lim0_bound_sample<V>(idx, g.b)) g.st(Tnew, g.rowbase + g.time_off(idx), v[idx]);
             } else if (kgADV) {
-                if (G_DPP(g)) mk_advance_dpp(ctx, g, a, v, Pcur, shz, c.it == 0, n1, d1, psum);
-                else mk_advance(ctx, g, a, v, Pcur, shz, c.it == 0, n1, d1, psum);
+                mk_advance(ctx, g, a, v, Pcur, shz, c.it == 0, n1, d1, psum);
                 if (!exact0) d0 = psum;              // exact denominator of the bound: sum Pch over the tile
             }
             if (c.it == 0) {
@@ -2449,13 +2253,6 @@ template <int LG, int V = 16, int CI = 0, int SG = SG_ALL, class Ctx> SSF_HD voi
     ctx.mark(0);
     ColGeom<T, LG, Ctx, false, V> g(ctx, a);
     cx<T> v[V];
-#if SSF_SPEC_G
-#pragma unroll
-    for (int q = 0; q < V; ++q) {                            // (the spectrum ahead of the control block: see col_body)
-        v[q] = g.ld(a.G, g.rowbase + g.freq_off(q));
-        if ((q & 3) == 3) ctx.issue_fence();
-    }
-#endif
     MkColStage st;
     mk_col_stage(ctx, a, st, SG);
     if (st.op < 0) return;
@@ -2472,15 +2269,11 @@ template <int LG, int V = 16, int CI = 0, int SG = SG_ALL, class Ctx> SSF_HD voi
     TwSrc<T> tws;
     GTw gtw;
     if (st.do_inv) {
-#if !SSF_SPEC_G
 #pragma unroll
         for (int q = 0; q < V; ++q) {
             v[q] = g.ld(a.G, g.rowbase + g.freq_off(q));
-#if SSF_LOAD_ORDER
             if ((q & 3) == 3) ctx.issue_fence();             // (appendix #43: the inter-pass twiddles are applied in this order, group by group)
-#endif
         }
-#endif
         // (the sample of the lim_0 bound is NOT fetched ahead here as col_body does: in this kernel it costs -0.3 ... -2.1 %, 4 of 4,
         //  where the double-precision stage gains +0.1 ... +1.3 %, 4 of 4: profiles/r5_ab_lim0_prefetch.txt)
         ctx.mark(1);

@@ -138,10 +138,7 @@ inline int fir_nfft(int K) {
     while (nfft < K) nfft <<= 1;
     return nfft;
 }
-#ifndef SSF_DELAY_NFFT
-#define SSF_DELAY_NFFT 2048
-#endif
-constexpr int kDelayNfft = SSF_DELAY_NFFT;   // block size of the 512-tap fractional-delay filters (delaySignal, polarisation delay, IQ skew)
+constexpr int kDelayNfft = 2048;          // block size of the 512-tap fractional-delay filters (delaySignal, polarisation delay, IQ skew)
 constexpr int kMaxNfft = 8192;            // c128 rows of the LDS transform (engine_fused_impl.h: k_ols)
 
 template <class Backend> struct RxCore {

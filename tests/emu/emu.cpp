@@ -33,7 +33,6 @@ struct EmuCtx {
     void flush(int) {}
     void issue_fence() {}
     template <int P> void setprio() {}
-    double xchg(double v);                    // the value thread tid ^ 1 passes (DevCtxCore::xchg: DPP)
     double wave_sum(double v) { return v; }
     double wave_max(double v) { return v; }
 };
@@ -92,7 +91,6 @@ struct Pool {
     Fiber *cur = nullptr;
     const std::function<void(EmuCtx &)> *body = nullptr;
     std::vector<char> lds;
-    std::vector<double> xch;
     ~Pool() {
         for (auto &x : f) free(x.stack);
     }
@@ -128,18 +126,8 @@ void EmuCtx::sync() {
     to_main(p, p.cur);
 }
 
-double EmuCtx::xchg(double v) {
-    Pool &p = g_pool;
-    p.xch[(size_t)tid] = v;
-    sync();
-    const double r = p.xch[(size_t)(tid ^ 1)];
-    sync();                                    // (nobody overwrites a value its partner has not read yet)
-    return r;
-}
-
 void run_block(int bid, int nblocks, int nthreads, size_t lds_bytes, const std::function<void(EmuCtx &)> &body) {
     Pool &p = g_pool;
-    if (p.xch.size() < (size_t)nthreads) p.xch.resize((size_t)nthreads);
     if ((int)p.f.size() < nthreads) {
         const size_t old = p.f.size();
         p.f.resize((size_t)nthreads);

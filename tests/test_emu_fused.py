@@ -138,7 +138,7 @@ def test_c64_kernels_have_no_coherent_amplitude_bias():
 
 def test_complex64_kernels_do_not_drift_over_a_full_span(monkeypatch):
     """1001 steps at N = 4096 on the emulated kernels against the complex128 oracle.  With twiddles rounded to one float
-    (round 1; -DSSF_C64_HILO=0) the kernels lose 1.4e-7 of power per step -- the mean magnitude error of the small, fixed
+    (round 1) the kernels lose 1.4e-7 of power per step -- the mean magnitude error of the small, fixed
     twiddle set of a 64-point pass, the same at every step -- and the reference's own complex64 path ends 6.8e-5 away from
     its complex128 result; with every factor applied as a hi + lo pair both complex64 pipelines (packed polarisation pairs,
     and one row per polarisation with SSF_C64_PACKED=0) stay below 2e-5 / 3e-5."""
