@@ -373,10 +373,10 @@ struct EmuBackend {
     void launch_optics(const ssf::rx::OpticsArgs &a) { run_grid(ew_grid(a.n), 64, 64, [&](EmuCtx &c) { ssf::rx::optics_body(c, a); }); }
     void launch_nlin_phase(const ssf::rx::NlinPhaseArgs &a) { run_grid(ew_grid(a.n), 64, 64, [&](EmuCtx &c) { ssf::rx::nlin_phase_body(c, a); }); }
     void launch_conv_sums(const ssf::rx::ConvSumsArgs &a, int nblocks) { run_grid(nblocks, 64, 4096, [&](EmuCtx &c) { ssf::rx::conv_sums_body(c, a); }); }
-    void launch_absmax(const ssf::rx::AbsMaxArgs &a, int nblocks) { run_grid(nblocks, 64, 4096, [&](EmuCtx &c) { ssf::rx::absmax_body(c, a); }); }
-    void launch_pn(const ssf::rx::PnArgs &a, int nchunks) { run_grid(nchunks, 64, 64 * sizeof(double), [&](EmuCtx &c) { ssf::rx::pn_body(c, a); }); }
-    void launch_iqm(const ssf::rx::IqmArgs &a, int nblocks) { run_grid(nblocks, 64, 4096, [&](EmuCtx &c) { ssf::rx::iqm_body(c, a); }); }
-    void launch_shift_add(const ssf::rx::ShiftAddArgs &a) { run_grid(ew_grid(a.N), 64, 64, [&](EmuCtx &c) { ssf::rx::shift_add_body(c, a); }); }
+    void launch_absmax(const ssf::rx::AbsMaxArgs &a, int nblocks) { ++launches; run_grid(nblocks, 64, 4096, [&](EmuCtx &c) { ssf::rx::absmax_body(c, a); }); }
+    void launch_pn(const ssf::rx::PnArgs &a, int nchunks) { ++launches; run_grid(nchunks, 64, 64 * sizeof(double), [&](EmuCtx &c) { ssf::rx::pn_body(c, a); }); }
+    void launch_iqm(const ssf::rx::IqmArgs &a, int nblocks) { ++launches; run_grid(nblocks, 64, 4096, [&](EmuCtx &c) { ssf::rx::iqm_body(c, a); }); }
+    void launch_shift_add(const ssf::rx::ShiftAddArgs &a) { ++launches; run_grid(ew_grid(a.N), 64, 64, [&](EmuCtx &c) { ssf::rx::shift_add_body(c, a); }); }
     void launch_chain_ols(const ssf::rx::ChainOlsArgs &a, int mode) {
         ++launches;
         const ssf::fused::OlsLaunch o = ssf::fused::ols_launch(a.o.log2nfft, a.o.nrows, a.o.njobs);
@@ -558,7 +558,7 @@ int emu_overlap_save(int64_t sigLen, int nrows, int lg, int K, const void *Hfft,
 }
 
 static long g_rx_launches = 0;
-long emu_rx_launches() { return g_rx_launches; }                   // kernel launches of the last emu_rx_run / emu_rx_chain / emu_fir_long
+long emu_rx_launches() { return g_rx_launches; }                   // kernel launches of the last emu_rx_run / emu_rx_chain / emu_fir_long / emu_wdm_tx
 int emu_rx_run(int mode, int64_t N, int nmodes, const ssf_rx_params *p, const void *in0, const void *lo, const double *un, void *out) {
     EmuBackend be;
     ssf::rx::RxCore<EmuBackend> core(be);
@@ -649,6 +649,7 @@ int emu_wdm_tx(const ssf_tx_params *p, const void *symbols, const double *taps, 
     EmuBackend be;
     ssf::rx::RxCore<EmuBackend> core(be);
     int rc = core.wdm_tx(*p, symbols, taps, phi, amp, deltaF, out, power_out);
+    g_rx_launches = be.launches;                                   // (0 after a refusal: every check comes before the first launch)
     if (rc) fprintf(stderr, "emu: %s\n", core.err.c_str());
     return rc;
 }
