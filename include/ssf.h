@@ -648,6 +648,58 @@ typedef struct {
 int  ssf_mimo_eq(int device, const ssf_eq_params *params, const ssf_eq_stage *stages, const double *const_tab, const double *radii_tab,
                  void *H_inout, const void *x, const void *ref, void *sig_out, double *errsq_out);
 
+/* ---- single-input adaptive equalizers of the direct-detection chain on the device (optic/dsp/equalization.py:1176-2143 dfe, ffe,
+ * volterra and their cores; optic/dsp/core.py:720 anorm), the stage between pnorm and fastBERcalc.
+ * One recursion covers the three equalizers: LMS over a regressor phi(k),  y = w . phi,  e = r - y,  w += mu_s e conj(phi), with r
+ * the training symbol while k < nTrain and otherwise the nearest table point (the first minimum of |y - c| in table order); the
+ * update happens while k < nTrain, or always with SSF_SISO_FULLTIME.
+ *   SSF_SISO_FFE       phi = window (nTaps samples)
+ *   SSF_SISO_DFE       phi = [window ; the last nFB references r, newest first, zeros at the start]
+ *   SSF_SISO_VOLTERRA  phi = [window ; w[t2+i] w[t2+j] ; w[t3+i] w[t3+j] w[t3+l] (order 3)], steps mu, mu / 2, mu / 7,
+ *                      t2 = (nTaps - n2) / 2, t3 = (nTaps - n3) / 2; real data only
+ *   SSF_SISO_ANORM     sig_out = x / max |x| (n values, float64 or complex128); everything but n, dtype, x and sig_out is ignored
+ *   x           n values of `dtype` (any ssf_metrics_dtype), host or device; never written.  The kernels divide by
+ *               sqrt(mean |x|^2) and round to single precision where prec32 is set (volterra: then divide by the maximum modulus
+ *               and round again) as they load; the nTaps / 2 zeros the reference pads at both ends are not stored
+ *   ref         nref values of ref_dtype (real with real x, complex with complex x), host or device; normalised by its own mean
+ *               power over all nref values; nref >= min(nTrain, N); may be NULL with nref = 0
+ *   const_tab   M (re, im) pairs, host: the decision table as the caller normalised it
+ *   coef_inout  ncoef values (float64, or complex128 for complex x), host: ffe f; dfe [f ; b]; volterra [h1 ; h2 row-major ;
+ *               h3 row-major (order 3 only)] -- the initial coefficients in, the final ones out
+ *   sig_out     N = n / SpS values, float64 or complex128, host or device (volterra: divided by sqrt(mean sig_out^2) at the end)
+ *   mse_out     N float64, host or device: |e|^2 of every symbol
+ * Symbol k of a pass reads stream[k SpS .. k SpS + nTaps): the padded input, whose SpS samples behind symbol k are zeros unless
+ * k SpS + nTaps + SpS < n + 2 (nTaps / 2).  With preconvIters > 1 and nTrain < N every pass but the last ends behind symbol nTrain
+ * and the next one starts from the window that pass ended with.
+ * One wavefront walks every symbol that adapts or feeds a later decision with ncoef / 64 coefficients per lane in registers;
+ * for SSF_SISO_FFE and SSF_SISO_VOLTERRA in SSF_SISO_DATA_AIDED mode the symbols of the last pass from nTrain on run one per
+ * thread with the coefficients fixed.  On return serial_symbols, parallel_symbols and R say what ran.
+ * Limits: ncoef <= 1536 (24 per lane), nTaps <= 256, nFB <= 256, 1 <= SpS <= 8, SpS <= nTaps, n2, n3 <= nTaps, 2 <= M <= 1024. */
+typedef enum { SSF_SISO_FFE = 0, SSF_SISO_DFE = 1, SSF_SISO_VOLTERRA = 2, SSF_SISO_ANORM = 3 } ssf_siso_kind;
+typedef enum { SSF_SISO_DATA_AIDED = 0, SSF_SISO_FULLTIME = 1 } ssf_siso_mode;
+typedef struct {
+    int64_t n;                    /* input samples */
+    int64_t nref;                 /* values of ref */
+    int64_t nTrain;
+    int32_t kind;                 /* ssf_siso_kind */
+    int32_t mode;                 /* ssf_siso_mode */
+    int32_t dtype, ref_dtype;     /* ssf_metrics_dtype */
+    int32_t prec32;               /* 1: normalised inputs are rounded to single precision */
+    int32_t order;                /* volterra: 2 or 3 */
+    int32_t nTaps;                /* nTaps, nTapsFF or n1Taps */
+    int32_t nFB, n2, n3;
+    int32_t SpS, M;
+    int32_t preconvIters;
+    int32_t ncoef;
+    int32_t no_frozen;            /* measurement aid: 1 keeps every symbol with the serial kernel */
+    int32_t R;                    /* out: coefficient slots per lane of the serial kernel, 0 if it did not run */
+    double  mu;
+    int64_t serial_symbols;       /* out: symbols the serial kernel walked, all passes */
+    int64_t parallel_symbols;     /* out: symbols of the frozen kernel */
+} ssf_siso_params;
+int  ssf_siso_eq(int device, ssf_siso_params *params, const double *const_tab, void *coef_inout, const void *x, const void *ref,
+                 void *sig_out, double *mse_out);
+
 /* ---- soft-decision FEC on the device: the soft demapper and the LDPC belief-propagation decoder that end the reference's chain
  * (optic/comm/metrics.py:198-239 calcLLR; optic/comm/fec.py:347-758 sumProductAlgorithm, minSumAlgorithm, decodeLDPC).
  *

@@ -6,6 +6,11 @@ Drop-in for the fiber-channel functions of OptiCommPy's ``optic.models.modelsGPU
 Python + numpy calling hand-written HIP kernels (gfx950) through the C ABI declared
 in ``include/ssf.h`` (``libssf_hip.so``).  There is no CPU fallback: without the
 library or without a GPU every propagation call raises.
+
+The receiver side is there as well, on numpy arrays and ``DeviceArray``s alike: the coherent chain (``pdmCoherentReceiver``,
+``decimate``, ``edc``, ``symbolSync``, ``mimoAdaptEqualizer``, ``cpr``, ``metrics``, ``calcLLR``, ``decodeLDPC``) and the
+equalizers of the direct-detection chain, ``ffe``, ``dfe`` and ``volterra`` with ``pnorm`` and ``anorm``
+(``opticommpy_amd.sisoeq``; also importable from ``opticommpy_amd.equalization``, as in the reference).
 """
 from .utils import parameters  # noqa: F401
 from .models import (  # noqa: F401
@@ -22,11 +27,13 @@ from .rx import (  # noqa: F401
 
 from .wdm_tx import basicLaserModel, grayMapping, phaseNoise, pulseShape, simpleWDMTx  # noqa: F401
 from . import metrics  # noqa: F401  (a callable module: oa.metrics(rx, tx, M, constType) returns all seven link metrics)
-from .metrics import calcEVM, demodulateGray, fastBERcalc, monteCarloGMI, monteCarloMI, pnorm, signalPower  # noqa: F401
+from .metrics import calcEVM, demodulateGray, fastBERcalc, monteCarloGMI, monteCarloMI, anorm, pnorm, signalPower  # noqa: F401
 from . import cpr  # noqa: F401  (a callable module: oa.cpr(sigIn, param) is the reference's cpr)
 from .cpr import bps, bpsGPU, fourthPowerFOE  # noqa: F401
 from .sync import finddelay, symbolSync  # noqa: F401
 from .equalization import mimoAdaptEqualizer  # noqa: F401
+from . import sisoeq  # noqa: F401
+from .sisoeq import dfe, ffe, volterra  # noqa: F401
 from .fec import calcLLR, decodeLDPC, encodeLDPC, modulateGray, par2gen, readAlist, triangP1P2, writeAlist  # noqa: F401
 from .ofdm import calcSymbolRate, demodulateOFDM, hermit, modulateOFDM, zeroPad  # noqa: F401
 from .perturbation import calcNLINperturbation, calcNLINperturbationSimplified, calcPertCoeffMatrix, perturbationNLIN  # noqa: F401
@@ -39,7 +46,7 @@ __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMa
            "opticalHybrid2x4", "coherentReceiver", "pdmCoherentReceiver", "pdmCoherentReceiverChain", "parameters", "ssfm", "manakovSSF", "manakovDBP", "nlinPhaseRot", "convergenceCondition", "edfa", "edc", "blockwiseFFTConv", "linearFiberChannel",
            "setPowerforParSSFM", "checkGPU", "last_run", "set_device", "set_engine",
            "metrics", "fastBERcalc", "monteCarloGMI", "monteCarloMI", "calcEVM", "demodulateGray", "pnorm", "signalPower",
-           "cpr", "bps", "bpsGPU", "fourthPowerFOE", "symbolSync", "finddelay", "mimoAdaptEqualizer", "calcLLR", "decodeLDPC", "readAlist",
+           "cpr", "bps", "bpsGPU", "fourthPowerFOE", "symbolSync", "finddelay", "mimoAdaptEqualizer", "ffe", "dfe", "volterra", "anorm", "calcLLR", "decodeLDPC", "readAlist",
            "encodeLDPC", "modulateGray", "par2gen", "triangP1P2", "writeAlist",
            "modulateOFDM", "demodulateOFDM", "hermit", "zeroPad", "calcSymbolRate",
            "calcPertCoeffMatrix", "calcNLINperturbation", "calcNLINperturbationSimplified", "perturbationNLIN",

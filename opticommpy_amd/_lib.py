@@ -235,6 +235,32 @@ def eq_chunk(nModes, nTaps, SpS):
     return min(EQ_CHUNK, (EQ_STAGE_ELEMS // nModes - nTaps) // SpS + 1)
 
 
+class SisoParams(C.Structure):
+    """ssf_siso_params (include/ssf.h)."""
+    _fields_ = [("n", C.c_int64), ("nref", C.c_int64), ("nTrain", C.c_int64), ("kind", C.c_int32), ("mode", C.c_int32),
+                ("dtype", C.c_int32), ("ref_dtype", C.c_int32), ("prec32", C.c_int32), ("order", C.c_int32), ("nTaps", C.c_int32),
+                ("nFB", C.c_int32), ("n2", C.c_int32), ("n3", C.c_int32), ("SpS", C.c_int32), ("M", C.c_int32),
+                ("preconvIters", C.c_int32), ("ncoef", C.c_int32), ("no_frozen", C.c_int32), ("R", C.c_int32), ("mu", C.c_double),
+                ("serial_symbols", C.c_int64), ("parallel_symbols", C.c_int64)]
+
+
+SISO_KINDS = {"ffe": 0, "dfe": 1, "volterra": 2, "anorm": 3}                                 # ssf_siso_kind
+SISO_MODES = {"data-aided": 0, "fulltime": 1}                                                # ssf_siso_mode
+SISO_MAX_COEFFS = 1536     # coefficients of one call: 24 per lane of the serial kernel (siso_kernels.h: kMaxCoeffs)
+SISO_MAX_TAPS = 256        # nTaps, nTapsFF, n1Taps (kMaxTaps)
+SISO_MAX_FB = 256          # nTapsFB (kMaxFb)
+SISO_MAX_SPS = 8           # (kMaxSpS)
+SISO_MAX_M = 1024          # points of the decision table the kernels stage (kMaxM)
+SISO_CHUNK = 64            # symbols the serial kernel stages per chunk (kChunk)
+SISO_TILE = 256            # symbols per workgroup of the frozen kernel (kTile)
+
+
+def siso_slots(ncoef):
+    """Coefficient slots per lane the serial kernel is compiled for (siso_kernels.h: slots_for)."""
+    r = (ncoef + 63) // 64
+    return next(v for v in (1, 2, 4, 8, 16, 24) if r <= v)
+
+
 METRICS_DTYPES = {"complex128": 0, "complex64": 1, "float64": 2, "float32": 3}              # ssf_metrics_dtype
 METRICS_BER, METRICS_GMI, METRICS_MI, METRICS_EVM, METRICS_EVM_BLIND = 1, 2, 4, 8, 16       # ssf_metrics_want
 
@@ -313,6 +339,8 @@ SYMBOLS = {
     "ssf_sync_transform_time": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_mimo_eq": (C.c_int, [C.c_int, C.POINTER(EqParams), C.POINTER(EqStage), C.POINTER(C.c_double), C.POINTER(C.c_double),
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_siso_eq": (C.c_int, [C.c_int, C.POINTER(SisoParams), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p]),
     "ssf_calc_llr": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "ssf_ldpc_graph_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

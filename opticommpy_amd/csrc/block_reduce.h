@@ -48,5 +48,26 @@ __device__ __forceinline__ double wave_sum_partials(const double *part, int nb, 
     return wave_sum_down(a);
 }
 
+// ---- the maximum of non-negative values over a launch, by the same route as the sums (a maximum does not depend on the order;
+// the route is fixed all the same)
+__device__ __forceinline__ double wave_max_down(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, 64));
+    return v;
+}
+__device__ inline void block_max_store(double v, double *out) {
+    __shared__ double sh[kWaves];
+    v = wave_max_down(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) *out = fmax(fmax(fmax(sh[0], sh[1]), sh[2]), sh[3]);
+}
+__device__ __forceinline__ double wave_max_partials(const double *part, int nb) {
+    double a = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 64) a = fmax(a, part[b]);
+    return wave_max_down(a);
+}
+
 }  // namespace br
 }  // namespace ssf

@@ -851,6 +851,53 @@ int ssf_mimo_eq(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, 
     return rc ? set_err(rc, "ssf_mimo_eq: " + err) : SSF_OK;
 }
 
+// ---- ffe, dfe, volterra, anorm (engine_siso.hip): every check comes before the first allocation or launch
+static const char *siso_bad(const ssf_siso_params *p, const void *ref) {
+    if (p->kind < SSF_SISO_FFE || p->kind > SSF_SISO_ANORM) return "unknown kind";
+    if (p->n < 1) return "n must be at least 1";
+    if (metrics_bad_dtype(p->dtype)) return "unknown dtype";
+    if (p->kind == SSF_SISO_ANORM) return nullptr;
+    const bool cx = p->dtype == SSF_M_C128 || p->dtype == SSF_M_C64;
+    if (p->mode != SSF_SISO_DATA_AIDED && p->mode != SSF_SISO_FULLTIME) return "unknown mode";
+    if (p->nTaps < 1 || p->nTaps > 256) return "nTaps must be 1 .. 256";
+    if (p->SpS < 1 || p->SpS > 8 || p->SpS > p->nTaps) return "SpS must be 1 .. 8 and at most nTaps";
+    if (p->n < p->SpS) return "n must be at least SpS";
+    if (p->M < 2 || p->M > 1024) return "M must be 2 .. 1024";
+    if (p->preconvIters < 1 || p->nTrain < 0) return "preconvIters >= 1 and nTrain >= 0";
+    if (!std::isfinite(p->mu)) return "mu must be finite";
+    int64_t ncoef = p->nTaps;
+    if (p->kind == SSF_SISO_DFE) {
+        if (p->nFB < 0 || p->nFB > 256) return "nFB must be 0 .. 256";
+        ncoef += p->nFB;
+    } else if (p->kind == SSF_SISO_VOLTERRA) {
+        if (cx) return "volterra takes real data";
+        if (p->order != 2 && p->order != 3) return "order must be 2 or 3";
+        if (p->n2 < 1 || p->n3 < 1 || p->n2 > p->nTaps || p->n3 > p->nTaps) return "n2 and n3 must be 1 .. nTaps";
+        ncoef += (int64_t)p->n2 * p->n2 + (p->order == 3 ? (int64_t)p->n3 * p->n3 * p->n3 : 0);
+    }
+    if (ncoef > 1536) return "more than 1536 coefficients";
+    if (p->ncoef != ncoef) return "ncoef does not match the geometry";
+    const int64_t N = p->n / p->SpS;
+    if (p->nref < (p->nTrain < N ? p->nTrain : N)) return "ref must hold min(nTrain, N) values";
+    if (p->nref > 0) {
+        if (!ref) return "ref is NULL";
+        if (metrics_bad_dtype(p->ref_dtype)) return "unknown ref_dtype";
+        if (cx != (p->ref_dtype == SSF_M_C128 || p->ref_dtype == SSF_M_C64)) return "x and ref must both be real or both complex";
+    }
+    return nullptr;
+}
+
+int ssf_siso_eq(int device, ssf_siso_params *p, const double *const_tab, void *coef_inout, const void *x, const void *ref,
+                void *sig_out, double *mse_out) {
+    if (!p || !x || !sig_out) return set_err(SSF_ERR_BAD_ARG, "ssf_siso_eq: NULL argument");
+    if (const char *m = siso_bad(p, ref)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_siso_eq: ") + m);
+    if (p->kind != SSF_SISO_ANORM && (!const_tab || !coef_inout || !mse_out)) return set_err(SSF_ERR_BAD_ARG, "ssf_siso_eq: NULL argument");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::siso_run(device, p, const_tab, coef_inout, x, ref, sig_out, mse_out, &err);
+    return rc ? set_err(rc, "ssf_siso_eq: " + err) : SSF_OK;
+}
+
 // ---- soft-decision FEC (engine_fec.hip): every check comes before the first allocation, upload or launch
 int ssf_calc_llr(int device, int64_t n, int32_t dtype, int32_t M, double sigma2, const double *const_tab, const int32_t *bitmap,
                  const double *px, const void *x, double *llr_out) {

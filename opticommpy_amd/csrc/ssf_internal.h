@@ -181,6 +181,9 @@ int sync_transform_time(int device, int64_t L, int nseq, int nslots, int nslots2
 // engine_eq.hip (arguments already checked by ssf_api.hip)
 int eq_run(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const double *table, const double *radii, void *H_inout,
            const void *x, const void *ref, void *sig_out, double *errsq_out, std::string *err);
+// engine_siso.hip (arguments already checked by ssf_api.hip)
+int siso_run(int device, ssf_siso_params *p, const double *table, void *coef_inout, const void *x, const void *ref, void *sig_out,
+             double *mse_out, std::string *err);
 // engine_fec.hip (arguments already checked by ssf_api.hip)
 int fec_calc_llr(int device, int64_t n, int dtype, int M, double sigma2, const double *table, const int32_t *bitmap, const double *px,
                  const void *x, double *llr_out, std::string *err);

@@ -41,9 +41,10 @@ import numpy as np
 from . import _lib
 from . import device as _dev
 from .cpr import _check_constellation
+from .sisoeq import dfe, ffe, volterra  # noqa: F401  (the reference keeps them in its equalization module)
 from .wdm_tx import grayMapping
 
-__all__ = ["mimoAdaptEqualizer"]
+__all__ = ["mimoAdaptEqualizer", "ffe", "dfe", "volterra"]
 
 MAX_MODES, MAX_TAPS, MAX_SPS = 4, 64, 8
 ALGS = tuple(_lib.EQ_ALGS)

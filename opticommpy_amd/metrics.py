@@ -1,7 +1,7 @@
 """Link metrics on the device: BER, SER, SNR, GMI, NGMI, MI and EVM of received against transmitted symbols.
 
 Drop-in for ``fastBERcalc``, ``monteCarloGMI``, ``monteCarloMI``, ``calcEVM`` (optic/comm/metrics.py:111-195, 329-493, 572-637),
-``demodulateGray`` (optic/comm/modulation.py:369-408), ``pnorm`` and ``signalPower`` (optic/dsp/core.py:69-85, 701-717), plus
+``demodulateGray`` (optic/comm/modulation.py:369-408), ``pnorm``, ``anorm`` and ``signalPower`` (optic/dsp/core.py:69-85, 701-736), plus
 ``metrics``, which returns all seven numbers of one library call (``ssf_metrics``, include/ssf.h): the symbols are normalised once
 and read once per pass, and only ``nModes`` result records come back from the GPU.  The four reference-named functions are that
 same call with a selection of what is wanted, so their values equal those of ``metrics`` bit for bit.
@@ -30,7 +30,7 @@ from . import _lib
 from . import device as _dev
 from .wdm_tx import grayMapping
 
-__all__ = ["fastBERcalc", "monteCarloGMI", "monteCarloMI", "calcEVM", "demodulateGray", "pnorm", "signalPower", "metrics"]
+__all__ = ["fastBERcalc", "monteCarloGMI", "monteCarloMI", "calcEVM", "demodulateGray", "pnorm", "anorm", "signalPower", "metrics"]
 
 _NAMES = ("BER", "SER", "SNR", "GMI", "NGMI", "MI", "EVM")
 
@@ -236,6 +236,20 @@ def pnorm(x):
     ptr, keep = _pointer(x)
     out = _dev.empty(_dev.is_device(x), x.shape, np.complex128 if x.dtype.kind == "c" else np.float64)
     _lib.raise_for(lib, None, lib.ssf_pnorm(_state["device"], x.size, _lib.METRICS_DTYPES[x.dtype.name], ptr, _dev.out_ptr(out)))
+    del keep
+    return out
+
+
+def anorm(x):
+    """x / max |x| over the whole array (optic/dsp/core.py:720-736), in double precision; the maximum is taken in a fixed order.
+    A DeviceArray gives a DeviceArray."""
+    from .models import _state
+    x = _flat(x)
+    lib = _lib.load()
+    ptr, keep = _pointer(x)
+    out = _dev.empty(_dev.is_device(x), x.shape, np.complex128 if x.dtype.kind == "c" else np.float64)
+    p = _lib.SisoParams(n=x.size, kind=_lib.SISO_KINDS["anorm"], dtype=_lib.METRICS_DTYPES[x.dtype.name])
+    _lib.raise_for(lib, None, lib.ssf_siso_eq(_state["device"], C.byref(p), None, None, ptr, None, _dev.out_ptr(out), None))
     del keep
     return out
 

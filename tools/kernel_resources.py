@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS use of every kernel of the fused engine, read from the gfx950 assembly metadata.
-    python tools/kernel_resources.py [extra hipcc flags ...]     (works without a GPU; ~2 min)"""
+    python tools/kernel_resources.py [extra hipcc flags ...]     (works without a GPU; ~2 min)
+    SSF_UNITS=engine_siso python tools/kernel_resources.py       (other translation units, comma-separated, with the Makefile's plain flags)"""
 import os
 import re
 import subprocess
@@ -15,12 +16,14 @@ def main():
     keep = os.environ.get("SSF_KEEP_ASM")                      # path prefix: keep / reuse the assembly listings
     txt = ""
     with tempfile.TemporaryDirectory() as td:
-        for unit in ("engine_fused_f64", "engine_fused_f32"):  # the two translation units that hold the kernels
+        fused = ("engine_fused_f64", "engine_fused_f32")      # the two translation units that hold the kernels
+        for unit in (os.environ["SSF_UNITS"].split(",") if os.environ.get("SSF_UNITS") else fused):
             asm = (keep + "." + unit + ".s") if keep else os.path.join(td, unit + ".s")
             if not (keep and os.path.exists(asm)):
                 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                                       "-I" + CSRC, "-Wno-pass-failed", "-mllvm", "-amdgpu-use-amdgpu-trackers=1",      # (the Makefile's FUSED_FLAGS)
-                                       "--cuda-device-only", "-S"] + sys.argv[1:] +
+                                       "-I" + CSRC, "-Wno-pass-failed"] +
+                                      (["-mllvm", "-amdgpu-use-amdgpu-trackers=1"] if unit in fused else []) +  # (the Makefile's FUSED_FLAGS)
+                                      ["--cuda-device-only", "-S"] + sys.argv[1:] +
                                       [os.path.join(CSRC, unit + ".hip"), "-o", asm], stderr=subprocess.DEVNULL)
             txt += open(asm).read()
     rows = []
