@@ -37,6 +37,10 @@
  *   ssf_fir_filter / ssf_fir_long / ssf_delay_signal / ssf_decimate / ssf_rx_run   receiver side, see below
  *   ssf_device_malloc / ssf_device_free / ssf_device_memcpy / ssf_device_axpy   device-resident arrays, see below
  *   ssf_wdm_tx                           simpleWDMTx signal path          optic/models/tx.py:178-217
+ *   ssf_pam_tx                           pamTransmitter signal path       optic/models/tx.py:317-342
+ *   ssf_modulate_optical                 pm, mzm, iqm                     optic/models/devices.py:56-220
+ *   ssf_awgn                             awgn                             optic/models/channels.py:522-565
+ *   ssf_upsample                         upsample, voa                    optic/dsp/core.py:395-432, devices.py:263-286
  *   ssf_device_copy_bandwidth            (no reference equivalent) measured memory ceiling
  *   ssf_set_profiling / ssf_get_kernel_times   time.time() pairs around calls in
  *                                        examples/benchmarck_GPU_processing.ipynb:389-395
@@ -483,6 +487,38 @@ typedef struct {
 } ssf_tx_params;
 int  ssf_wdm_tx(int device, const ssf_tx_params *params, const void *symbols, const double *taps, const double *phi,
                 const double *amp, const double *deltaF, void *sig_out, double *power_out);
+
+/* ---- IM/DD transmitter and AWGN channel.  Array arguments marked (host or device) may be device pointers; a device array never
+ * leaves the device.  Every refusal is a status with a message (ssf_last_error(NULL)) before anything runs on the GPU.
+ *   ssf_pam_tx            the signal path of pamTransmitter, optic/models/tx.py:317-342, for every polarisation mode: zero-stuffing +
+ *       pulse-shaping FIR (one overlap-save launch), a peak pass, mzm(1, mzmScale * Vpi * sig / max|sig|, Vpi, Vb, ER) with the
+ *       partial sums of its power, and sig_out[:, mode] = amp * pnorm(.): four launches per mode and one host wait at the end.
+ *       symbols (nPolModes, nSymbols) float64 and taps (ntaps <= 4096) float64 on the host; Vb is the bias as calcMZM takes it
+ *       (pamTransmitter passes -mzmVb); amp = sqrt(dBm2W(power)); sig_out (nSymbols * SpS, nPolModes) complex128 (host or device).
+ *   ssf_modulate_optical  pm / mzm / iqm, optic/models/devices.py:56-220 (calcPM / calcMZM, optic/dsp/core.py:1076-1139), one
+ *       element-wise launch.  kind: SSF_MOD_*; u: n values of u_dtype (SSF_M_F64 or SSF_M_C128; host or device) -- a
+ *       complex drive is put through exp(1j * (z / Vpi) * pi) as written, iqm takes its real and imaginary parts; Ei: n complex128
+ *       (host or device) or NULL for the scalar (Ei_re, Ei_im); pm reads Vpi; mzm reads Vpi, VbI, ERI; iqm reads all.  gamma is
+ *       derived from the extinction ratios [dB] on the host in double precision, as calcMZM does.  out: n complex128.
+ *   ssf_awgn              awgn, optic/models/channels.py:522-565, on n samples of ncols columns (row-major): sigma^2 = Fs_over_B *
+ *       mean(|sig|^2 over every element) / snr_lin, out = sig + sqrt(sigma^2 / 2) * (zr + 1j zi); zi = 0 unless complex_noise.
+ *       Two launches (fixed-order partial sums of the power; the noise pass adds them up itself) and no host wait in between.
+ *       unit_normals != NULL (host or device): n * ncols float64 for zr, followed by as many for zi when complex_noise -- the
+ *       caller's np.random.standard_normal draws; NULL and rng_seed != 0: Philox4x32-10 (counter = sample, row = column, a span
+ *       tag of its own), statistical parity as in ssf_edfa.  in_dtype / out_dtype: SSF_M_F64 or SSF_M_C128; a
+ *       float64 result needs a float64 signal and real noise.
+ *   ssf_upsample          upsample, optic/dsp/core.py:395-432, and voa, optic/models/devices.py:263-286: out (rows * factor, w) =
+ *       scale * in (rows, w) in the rows that are multiples of factor, zeros elsewhere, on rows of w 8-byte words (a float64 or
+ *       complex64 column is one word, a complex128 column two).  scale == 1 copies the bits; any other scale multiplies float64
+ *       values (float64 and complex128 arrays only). */
+enum { SSF_MOD_PM = 0, SSF_MOD_MZM = 1, SSF_MOD_IQM = 2 };
+int  ssf_pam_tx(int device, int64_t nSymbols, int32_t SpS, int32_t nPolModes, int32_t ntaps, const double *symbols,
+                const double *taps, double mzmScale, double Vpi, double Vb, double ER, double amp, void *sig_out);
+int  ssf_modulate_optical(int device, int32_t kind, int64_t n, int32_t u_dtype, const void *u, const void *Ei, double Ei_re,
+                          double Ei_im, double Vpi, double VbI, double VbQ, double Vphi, double ERI, double ERQ, void *out);
+int  ssf_awgn(int device, int64_t n, int32_t ncols, int32_t in_dtype, int32_t out_dtype, int32_t complex_noise, double Fs_over_B,
+              double snr_lin, const void *sig_in, const void *unit_normals, int64_t rng_seed, void *sig_out);
+int  ssf_upsample(int device, int64_t rows, int32_t w, int32_t factor, double scale, const void *in, void *out);
 
 /* ---- link metrics: BER, SER, SNR, GMI, NGMI, MI and EVM of received against transmitted symbols, evaluated on the device
  * (optic/comm/metrics.py:111-195 fastBERcalc, 329-426 monteCarloGMI, 429-547 monteCarloMI, 572-637 calcEVM).  One call

@@ -11,6 +11,11 @@ The receiver side is there as well, on numpy arrays and ``DeviceArray``s alike: 
 ``decimate``, ``edc``, ``symbolSync``, ``mimoAdaptEqualizer``, ``cpr``, ``metrics``, ``calcLLR``, ``decodeLDPC``) and the
 equalizers of the direct-detection chain, ``ffe``, ``dfe`` and ``volterra`` with ``pnorm`` and ``anorm``
 (``opticommpy_amd.sisoeq``; also importable from ``opticommpy_amd.equalization``, as in the reference).
+
+The front of the direct-detection notebooks is there too (``opticommpy_amd.imddtx``): ``pamTransmitter``, the modulators ``pm``,
+``mzm`` and ``iqm``, ``voa``, ``upsample`` and the ``awgn`` channel on numpy arrays and ``DeviceArray``s, and the host-side sources
+``bitSource``, ``prbsGenerator`` and ``symbolSource``; also importable from ``opticommpy_amd.tx``, ``.devices``, ``.channels``,
+``.core`` and ``.sources``, as in the reference.
 """
 from .utils import parameters  # noqa: F401
 from .models import (  # noqa: F401
@@ -37,6 +42,8 @@ from .sisoeq import dfe, ffe, volterra  # noqa: F401
 from .fec import calcLLR, decodeLDPC, encodeLDPC, modulateGray, par2gen, readAlist, triangP1P2, writeAlist  # noqa: F401
 from .ofdm import calcSymbolRate, demodulateOFDM, hermit, modulateOFDM, zeroPad  # noqa: F401
 from .perturbation import calcNLINperturbation, calcNLINperturbationSimplified, calcPertCoeffMatrix, perturbationNLIN  # noqa: F401
+from . import imddtx  # noqa: F401
+from .imddtx import awgn, bitSource, iqm, mzm, pamTransmitter, pm, prbsGenerator, symbolSource, upsample, voa  # noqa: F401
 from . import clock  # noqa: F401
 from .clock import (  # noqa: F401
     adc, calcClockDrift, clockSamplingInterp, dac, gardnerClockRecovery, gardnerTED, gardnerTEDnyquist, interpolator, quantizer, resample,
@@ -51,4 +58,5 @@ __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMa
            "modulateOFDM", "demodulateOFDM", "hermit", "zeroPad", "calcSymbolRate",
            "calcPertCoeffMatrix", "calcNLINperturbation", "calcNLINperturbationSimplified", "perturbationNLIN",
            "clockSamplingInterp", "quantizer", "resample", "adc", "dac", "gardnerClockRecovery", "calcClockDrift", "gardnerTED",
-           "gardnerTEDnyquist", "interpolator"]
+           "gardnerTEDnyquist", "interpolator",
+           "pamTransmitter", "mzm", "pm", "iqm", "voa", "upsample", "awgn", "bitSource", "prbsGenerator", "symbolSource"]

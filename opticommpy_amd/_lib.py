@@ -261,6 +261,12 @@ def siso_slots(ncoef):
     return next(v for v in (1, 2, 4, 8, 16, 24) if r <= v)
 
 
+MOD_KINDS = {"pm": 0, "mzm": 1, "iqm": 2}                                                   # SSF_MOD_*
+TX_BLOCK = 256             # lanes per workgroup of the IM/DD transmitter's and the AWGN channel's kernels (imddtx_kernels.h: kTxBlock)
+TX_BLOCKS = 1024           # most workgroups of their reduction passes (kTxBlocks)
+TX_EW_BLOCKS = 4096        # most workgroups of their element-wise passes: the grid-stride span is TX_EW_BLOCKS * TX_BLOCK elements
+TX_MAX_TAPS = 4096         # pulse-shaping taps of one overlap-save launch (rx_pipeline.h: kMaxNfft / 2)
+
 METRICS_DTYPES = {"complex128": 0, "complex64": 1, "float64": 2, "float32": 3}              # ssf_metrics_dtype
 METRICS_BER, METRICS_GMI, METRICS_MI, METRICS_EVM, METRICS_EVM_BLIND = 1, 2, 4, 8, 16       # ssf_metrics_want
 
@@ -323,6 +329,13 @@ SYMBOLS = {
                                C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_int32)]),
     "ssf_wdm_tx": (C.c_int, [C.c_int, C.POINTER(TxParams), C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.POINTER(C.c_double)]),
+    "ssf_pam_tx": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                             C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "ssf_modulate_optical": (C.c_int, [C.c_int, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                       C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p]),
+    "ssf_awgn": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p,
+                           C.c_void_p, C.c_int64, C.c_void_p]),
+    "ssf_upsample": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_void_p, C.c_void_p]),
     "ssf_metrics": (C.c_int, [C.c_int, C.POINTER(MetricsParams), C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double),
                               C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(MetricsResult)]),
     "ssf_pnorm": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),

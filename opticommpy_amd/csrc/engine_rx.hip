@@ -79,6 +79,34 @@ __global__ void __launch_bounds__(256) k_tx_shift_add(const ShiftAddArgs a) {
     SSF_RX_CTX();
     shift_add_body(ctx, a);
 }
+__global__ void __launch_bounds__(256) k_tx_pam_peak(const PamPeakArgs a) {
+    SSF_RX_CTX();
+    pam_peak_body(ctx, a);
+}
+__global__ void __launch_bounds__(256) k_tx_pam_mzm(const PamMzmArgs a) {
+    SSF_RX_CTX();
+    pam_mzm_body(ctx, a);
+}
+__global__ void __launch_bounds__(256) k_tx_pam_finish(const PamFinishArgs a) {
+    SSF_RX_CTX();
+    pam_finish_body(ctx, a);
+}
+__global__ void __launch_bounds__(256) k_tx_modulate(const ModArgs a) {
+    SSF_RX_CTX();
+    modulate_body(ctx, a);
+}
+__global__ void __launch_bounds__(256) k_power(const PowerArgs a) {
+    SSF_RX_CTX();
+    power_body(ctx, a);
+}
+__global__ void __launch_bounds__(256) k_awgn(const AwgnArgs a) {
+    SSF_RX_CTX();
+    awgn_body(ctx, a);
+}
+__global__ void __launch_bounds__(256) k_stuff(const StuffArgs a) {
+    SSF_RX_CTX();
+    stuff_body(ctx, a);
+}
 template <int LG, int C, int MODE> __global__ void __launch_bounds__(fused::ols_threads(LG, C)) k_rx_chain_ols(const ChainOlsArgs a) {
     SSF_RX_CTX();
     chain_ols_body<LG, C, MODE>(ctx, a);
@@ -226,6 +254,35 @@ struct HipRxBackend {
     void launch_shift_add(const ShiftAddArgs &a) {
         k_tx_shift_add<<<ew_grid(a.N), 256, 0, st>>>(a);
         chk(hipGetLastError(), "launch k_tx_shift_add");
+    }
+    // the IM/DD transmitter and the AWGN channel (imddtx_kernels.h): kTxBlock lanes, 4 KiB of LDS for the reductions
+    void launch_pam_peak(const PamPeakArgs &a, int nblocks) {
+        k_tx_pam_peak<<<(unsigned)nblocks, kTxBlock, 4096, st>>>(a);
+        chk(hipGetLastError(), "launch k_tx_pam_peak");
+    }
+    void launch_pam_mzm(const PamMzmArgs &a, int nblocks) {
+        k_tx_pam_mzm<<<(unsigned)nblocks, kTxBlock, 4096, st>>>(a);
+        chk(hipGetLastError(), "launch k_tx_pam_mzm");
+    }
+    void launch_pam_finish(const PamFinishArgs &a, int nblocks) {
+        k_tx_pam_finish<<<(unsigned)nblocks, kTxBlock, 4096, st>>>(a);
+        chk(hipGetLastError(), "launch k_tx_pam_finish");
+    }
+    void launch_modulate(const ModArgs &a) {
+        k_tx_modulate<<<(unsigned)tx_ew_blocks(a.n), kTxBlock, 0, st>>>(a);
+        chk(hipGetLastError(), "launch k_tx_modulate");
+    }
+    void launch_power(const PowerArgs &a, int nblocks) {
+        k_power<<<(unsigned)nblocks, kTxBlock, 4096, st>>>(a);
+        chk(hipGetLastError(), "launch k_power");
+    }
+    void launch_awgn(const AwgnArgs &a) {
+        k_awgn<<<(unsigned)tx_ew_blocks(a.total), kTxBlock, 4096, st>>>(a);
+        chk(hipGetLastError(), "launch k_awgn");
+    }
+    void launch_stuff(const StuffArgs &a) {
+        k_stuff<<<(unsigned)tx_ew_blocks(a.total), kTxBlock, 0, st>>>(a);
+        chk(hipGetLastError(), "launch k_stuff");
     }
     void launch_chain_ols(const ChainOlsArgs &a, int mode) {
         const fused::OlsLaunch o = fused::ols_launch(a.o.log2nfft, a.o.nrows, a.o.njobs);
@@ -403,6 +460,21 @@ int rx_delay(int device, int64_t N, double delay, double Fs, const void *in, voi
 int tx_wdm(int device, const ssf_tx_params *p, const void *symbols, const double *taps, const double *phi, const double *amp,
            const double *deltaF, void *out, double *power_out, std::string *err) {
     return with_core(device, err, [&](RxCore<Pooled> &c) { return c.wdm_tx(*p, symbols, taps, phi, amp, deltaF, out, power_out); });
+}
+int tx_pam(int device, int64_t nSymbols, int SpS, int nPolModes, int ntaps, const double *symbols, const double *taps, double mzmScale,
+           double Vpi, double Vb, double ER, double amp, void *out, std::string *err) {
+    return with_core(device, err, [&](RxCore<Pooled> &c) { return c.pam_tx(nSymbols, SpS, nPolModes, ntaps, symbols, taps, mzmScale, Vpi, Vb, ER, amp, out); });
+}
+int tx_modulate(int device, int kind, int64_t n, int u_cx, const void *u, const void *Ei, double ei_re, double ei_im, double Vpi, double VbI,
+                double VbQ, double Vphi, double ERI, double ERQ, void *out, std::string *err) {
+    return with_core(device, err, [&](RxCore<Pooled> &c) { return c.modulate(kind, n, u_cx, u, Ei, ei_re, ei_im, Vpi, VbI, VbQ, Vphi, ERI, ERQ, out); });
+}
+int ch_awgn(int device, int64_t n, int ncols, int in_cx, int out_cx, int cnoise, double FsB, double snr_lin, const void *x, const void *un,
+            unsigned long long seed, void *out, std::string *err) {
+    return with_core(device, err, [&](RxCore<Pooled> &c) { return c.awgn(n, ncols, in_cx, out_cx, cnoise, FsB, snr_lin, x, un, seed, out); });
+}
+int tx_stuff(int device, int64_t rows, int w, int factor, double scale, const void *in, void *out, std::string *err) {
+    return with_core(device, err, [&](RxCore<Pooled> &c) { return c.stuff(rows, w, factor, scale, in, out); });
 }
 int rx_chain(int device, int64_t N, const ssf_rx_params *p, const void *Es, const void *Elo, const void *taps, int ntaps, int SpSin,
              int decFactor, const void *edcH, int edcK, int edc_nfft, void *out, int32_t *sampDelay, std::string *err) {

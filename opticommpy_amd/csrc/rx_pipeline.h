@@ -16,6 +16,7 @@
 
 #include "fused_kernels.h"
 #include "rx_kernels.h"
+#include "imddtx_kernels.h"
 #include "ssf.h"
 
 namespace ssf {
@@ -852,6 +853,106 @@ template <class Backend> struct RxCore {
         be.sync();
         be.d2h_big(out, acc, sizeof(Cd) * (size_t)N * nPol);
         return be.ok() ? SSF_OK : fail(SSF_ERR_HIP, be.last_error());
+    }
+
+    // ---- IM/DD transmitter and AWGN channel (imddtx_kernels.h).  Arrays of any element type, by their bytes:
+    const void *resident_bytes(const void *p, size_t bytes) {
+        if (be.is_resident(p)) return p;
+        void *d = dalloc((bytes + sizeof(Cd) - 1) / sizeof(Cd));
+        if (d) be.h2d_big(d, p, bytes);
+        return d;
+    }
+    void *result_bytes(void *out, size_t bytes) { return be.is_resident(out) ? out : (void *)dalloc((bytes + sizeof(Cd) - 1) / sizeof(Cd)); }
+    int finish_bytes(void *out, const void *res, size_t bytes) {
+        be.sync();
+        if (!be.ok()) return fail(SSF_ERR_HIP, be.last_error());
+        if (res != out) be.d2h_big(out, res, bytes);
+        return be.ok() ? SSF_OK : fail(SSF_ERR_HIP, be.last_error());
+    }
+
+    // pamTransmitter's signal path (tx.py:317-342) for every mode: symbols (nPol, nSymbols) float64 and taps (ntaps) on the host,
+    // out (N, nPol) complex128, N = nSymbols * SpS.  Four launches per mode back to back; the one host wait is the last line.
+    int pam_tx(long long nS, int SpS, int nPol, int K, const double *symbols, const double *taps, double mzmScale, double Vpi, double Vb,
+               double ER, double amp, void *out) {
+        if (nS < 1 || SpS < 1 || nPol < 1 || K < 1) return fail(SSF_ERR_BAD_ARG, "ssf_pam_tx: bad size");
+        if (K > kMaxNfft / 2) return fail(SSF_ERR_UNSUPPORTED, "ssf_pam_tx: at most 4096 pulse-shaping taps");
+        const long long N = nS * SpS;
+        const int nfft = fir_nfft(K), nb = tx_blocks(N);
+        std::vector<zc> tz((size_t)K), sz((size_t)nPol * nS);
+        for (int i = 0; i < K; ++i) tz[(size_t)i] = zc(taps[i], 0.0);
+        for (size_t i = 0; i < sz.size(); ++i) sz[i] = zc(symbols[i], 0.0);
+        Cd *dH = taps_filter(tz.data(), K, nfft), *dsym = dalloc(sz.size()), *sig = dalloc((size_t)N);
+        Cd *res = (Cd *)result_bytes(out, sizeof(Cd) * (size_t)N * nPol);
+        double *part = (double *)dalloc((size_t)nb);                 // nb maxima, then nb sums
+        if (!dH || !dsym || !sig || !res || !part) return fail(SSF_ERR_OOM, "out of device memory");
+        be.h2d_big(dsym, sz.data(), sizeof(Cd) * sz.size());
+        double sp, sm;
+        mzm_arms(ER, &sp, &sm);
+        for (int mode = 0; mode < nPol; ++mode) {
+            int rc = ols(dsym + (size_t)mode * nS, 1, N, N, sig, 1, N, 1, dH, 0, K, nfft, 0, SpS);
+            if (rc) return rc;
+            be.launch_pam_peak(PamPeakArgs{sig, part, N}, nb);
+            be.launch_pam_mzm(PamMzmArgs{sig, res, part, part + nb, N, nb, nPol, mode, mzmScale, Vpi, Vb, sp, sm}, nb);
+            be.launch_pam_finish(PamFinishArgs{res, part + nb, N, nb, nPol, mode, amp}, nb);
+        }
+        return finish_bytes(out, res, sizeof(Cd) * (size_t)N * nPol);
+    }
+
+    // pm / mzm / iqm (devices.py:56-220): u n float64 or complex128 (u_cx), Ei n complex128 or null for the scalar (ei_re, ei_im)
+    int modulate(int kind, long long n, int u_cx, const void *u, const void *Ei, double ei_re, double ei_im, double Vpi, double VbI,
+                 double VbQ, double Vphi, double ERI, double ERQ, void *out) {
+        if (n < 1 || kind < MOD_PM || kind > MOD_IQM || !(Vpi != 0)) return fail(SSF_ERR_BAD_ARG, "ssf_modulate_optical: bad argument");
+        const double *du = (const double *)resident_bytes(u, sizeof(double) * (size_t)n * (u_cx ? 2 : 1));
+        const Cd *dE = Ei ? (const Cd *)resident_bytes(Ei, sizeof(Cd) * (size_t)n) : nullptr;
+        Cd *res = (Cd *)result_bytes(out, sizeof(Cd) * (size_t)n);
+        if (!du || (Ei && !dE) || !res) return fail(SSF_ERR_OOM, "out of device memory");
+        const ModArgs a = mod_args(kind, n, u_cx, du, dE, ei_re, ei_im, Vpi, VbI, VbQ, Vphi, ERI, ERQ, res);
+        be.launch_modulate(a);
+        return finish_bytes(out, a.out, sizeof(Cd) * (size_t)n);
+    }
+
+    // awgn (channels.py:522-565) on n samples of ncols columns: power pass, then the noise pass that adds the partials itself.
+    // un: unit normals on the host or the device (n ncols, twice that for complex noise), or null with a non-zero seed
+    int awgn(long long n, int ncols, int in_cx, int out_cx, int cnoise, double FsB, double snr_lin, const void *x, const void *un,
+             unsigned long long seed, void *out) {
+        if (n < 1 || ncols < 1 || !(FsB > 0) || !(snr_lin > 0) || (!un && seed == 0) || (!out_cx && (in_cx || cnoise)))
+            return fail(SSF_ERR_BAD_ARG, "ssf_awgn: bad argument");
+        const long long total = n * ncols;
+        const int nb = tx_blocks(total * (in_cx ? 2 : 1));
+        AwgnArgs a{};
+        a.x = (const double *)resident_bytes(x, sizeof(double) * (size_t)total * (in_cx ? 2 : 1));
+        a.un = un ? (const double *)resident_bytes(un, sizeof(double) * (size_t)total * (cnoise ? 2 : 1)) : nullptr;
+        a.out = (double *)result_bytes(out, sizeof(double) * (size_t)total * (out_cx ? 2 : 1));
+        double *part = (double *)dalloc((size_t)(nb + 1) / 2);
+        if (!a.x || (un && !a.un) || !a.out || !part) return fail(SSF_ERR_OOM, "out of device memory");
+        a.part = part;
+        a.total = total;
+        a.nb = nb;
+        a.ncols = ncols;
+        a.in_cx = in_cx;
+        a.out_cx = out_cx;
+        a.cnoise = cnoise;
+        a.FsB = FsB;
+        a.snr_lin = snr_lin;
+        a.seed = seed;
+        be.launch_power(PowerArgs{a.x, part, total * (in_cx ? 2 : 1)}, nb);
+        be.launch_awgn(a);
+        return finish_bytes(out, a.out, sizeof(double) * (size_t)total * (out_cx ? 2 : 1));
+    }
+
+    // upsample (core.py:395-432) and voa (devices.py:263-286) on rows of w 8-byte words
+    int stuff(long long rows, int w, int factor, double scale, const void *in, void *out) {
+        if (rows < 1 || w < 1 || factor < 1) return fail(SSF_ERR_BAD_ARG, "ssf_upsample: bad size");
+        StuffArgs a{};
+        a.total = rows * factor * w;
+        a.in = (const double *)resident_bytes(in, sizeof(double) * (size_t)rows * w);
+        a.out = (double *)result_bytes(out, sizeof(double) * (size_t)a.total);
+        if (!a.in || !a.out) return fail(SSF_ERR_OOM, "out of device memory");
+        a.factor = factor;
+        a.w = w;
+        a.scale = scale;
+        be.launch_stuff(a);
+        return finish_bytes(out, a.out, sizeof(double) * (size_t)a.total);
     }
 
     // decimate (core.py:435-491); sampDelay_out[ncols] receives the chosen sampling phases

@@ -672,6 +672,66 @@ int ssf_wdm_tx(int device, const ssf_tx_params *params, const void *symbols, con
     return rc ? set_err(rc, "ssf_wdm_tx: " + err) : SSF_OK;
 }
 
+// ---- IM/DD transmitter and AWGN channel (engine_rx.hip, imddtx_kernels.h): every check comes before the first allocation or launch
+static bool tx_real_or_complex(int32_t dtype) { return dtype == SSF_M_F64 || dtype == SSF_M_C128; }
+
+int ssf_pam_tx(int device, int64_t nSymbols, int32_t SpS, int32_t nPolModes, int32_t ntaps, const double *symbols, const double *taps,
+               double mzmScale, double Vpi, double Vb, double ER, double amp, void *sig_out) {
+    if (!symbols || !taps || !sig_out) return set_err(SSF_ERR_BAD_ARG, "ssf_pam_tx: NULL argument");
+    if (nSymbols < 1 || SpS < 1 || nPolModes < 1 || ntaps < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_pam_tx: sizes must be at least 1");
+    if (ntaps > 4096) return set_err(SSF_ERR_UNSUPPORTED, "ssf_pam_tx: at most 4096 pulse-shaping taps");
+    if (nSymbols > (int64_t)1 << 40 || nSymbols * SpS > (int64_t)1 << 40) return set_err(SSF_ERR_BAD_ARG, "ssf_pam_tx: too many samples");
+    if (!(Vpi != 0) || !std::isfinite(Vpi) || !std::isfinite(Vb) || !std::isfinite(ER) || !std::isfinite(mzmScale) || !std::isfinite(amp))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_pam_tx: Vpi must be non-zero and every modulator parameter finite");
+    if (int rc = rx_check_device(device)) return rc;
+    if (ssf::on_device(symbols) || ssf::on_device(taps)) return set_err(SSF_ERR_BAD_ARG, "ssf_pam_tx: symbols and taps are host arrays");
+    std::string err;
+    int rc = ssf::tx_pam(device, nSymbols, SpS, nPolModes, ntaps, symbols, taps, mzmScale, Vpi, Vb, ER, amp, sig_out, &err);
+    return rc ? set_err(rc, "ssf_pam_tx: " + err) : SSF_OK;
+}
+
+int ssf_modulate_optical(int device, int32_t kind, int64_t n, int32_t u_dtype, const void *u, const void *Ei, double Ei_re, double Ei_im,
+                         double Vpi, double VbI, double VbQ, double Vphi, double ERI, double ERQ, void *out) {
+    if (!u || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate_optical: NULL argument");
+    if (kind < SSF_MOD_PM || kind > SSF_MOD_IQM) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate_optical: kind is SSF_MOD_PM, SSF_MOD_MZM or SSF_MOD_IQM");
+    if (n < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate_optical: n must be at least 1");
+    if (!tx_real_or_complex(u_dtype)) return set_err(SSF_ERR_UNSUPPORTED, "ssf_modulate_optical: the drive is float64 or complex128");
+    if (!(Vpi != 0) || !std::isfinite(Vpi)) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate_optical: Vpi must be finite and non-zero");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::tx_modulate(device, kind, n, u_dtype == SSF_M_C128, u, Ei, Ei_re, Ei_im, Vpi, VbI, VbQ, Vphi, ERI, ERQ, out, &err);
+    return rc ? set_err(rc, "ssf_modulate_optical: " + err) : SSF_OK;
+}
+
+int ssf_awgn(int device, int64_t n, int32_t ncols, int32_t in_dtype, int32_t out_dtype, int32_t complex_noise, double Fs_over_B,
+             double snr_lin, const void *sig_in, const void *unit_normals, int64_t rng_seed, void *sig_out) {
+    if (!sig_in || !sig_out) return set_err(SSF_ERR_BAD_ARG, "ssf_awgn: NULL argument");
+    if (n < 1 || ncols < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_awgn: sizes must be at least 1");
+    if (!tx_real_or_complex(in_dtype) || !tx_real_or_complex(out_dtype)) return set_err(SSF_ERR_UNSUPPORTED, "ssf_awgn: float64 or complex128 arrays");
+    if (out_dtype == SSF_M_F64 && (in_dtype != SSF_M_F64 || complex_noise))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_awgn: a float64 result needs a float64 signal and real noise");
+    if (!(Fs_over_B > 0) || !std::isfinite(Fs_over_B)) return set_err(SSF_ERR_BAD_ARG, "ssf_awgn: Fs / B must be positive and finite");
+    if (!(snr_lin > 0) || !std::isfinite(snr_lin)) return set_err(SSF_ERR_BAD_ARG, "ssf_awgn: the linear SNR must be positive and finite");
+    if (!unit_normals && rng_seed == 0) return set_err(SSF_ERR_BAD_ARG, "ssf_awgn: unit normals or a non-zero rng_seed");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::ch_awgn(device, n, ncols, in_dtype == SSF_M_C128, out_dtype == SSF_M_C128, complex_noise != 0, Fs_over_B, snr_lin, sig_in,
+                          unit_normals, (unsigned long long)rng_seed, sig_out, &err);
+    return rc ? set_err(rc, "ssf_awgn: " + err) : SSF_OK;
+}
+
+int ssf_upsample(int device, int64_t rows, int32_t w, int32_t factor, double scale, const void *in, void *out) {
+    if (!in || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_upsample: NULL argument");
+    if (rows < 1 || w < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_upsample: sizes must be at least 1");
+    if (factor < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_upsample: the factor must be at least 1");
+    if (!std::isfinite(scale)) return set_err(SSF_ERR_BAD_ARG, "ssf_upsample: the scale must be finite");
+    if (in == out && factor > 1) return set_err(SSF_ERR_BAD_ARG, "ssf_upsample: in place only with factor 1");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::tx_stuff(device, rows, w, factor, scale, in, out, &err);
+    return rc ? set_err(rc, "ssf_upsample: " + err) : SSF_OK;
+}
+
 // ---- link metrics (engine_metrics.hip): every check comes before the first allocation or launch
 static bool metrics_bad_M(int32_t M) { return M < 2 || M > 1024 || (M & (M - 1)) != 0; }
 static bool metrics_bad_dtype(int32_t d) { return d < SSF_M_C128 || d > SSF_M_F32; }

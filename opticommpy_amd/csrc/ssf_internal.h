@@ -157,6 +157,14 @@ int mk_convergence(int device, int64_t n, const void *xfd, const void *yfd, cons
                    std::string *err);
 int tx_wdm(int device, const ssf_tx_params *p, const void *symbols, const double *taps, const double *phi, const double *amp,
            const double *deltaF, void *out, double *power_out, std::string *err);
+// the IM/DD transmitter and the AWGN channel (imddtx_kernels.h; arguments already checked by ssf_api.hip)
+int tx_pam(int device, int64_t nSymbols, int SpS, int nPolModes, int ntaps, const double *symbols, const double *taps, double mzmScale,
+           double Vpi, double Vb, double ER, double amp, void *out, std::string *err);
+int tx_modulate(int device, int kind, int64_t n, int u_cx, const void *u, const void *Ei, double ei_re, double ei_im, double Vpi, double VbI,
+                double VbQ, double Vphi, double ERI, double ERQ, void *out, std::string *err);
+int ch_awgn(int device, int64_t n, int ncols, int in_cx, int out_cx, int cnoise, double FsB, double snr_lin, const void *x, const void *un,
+            unsigned long long seed, void *out, std::string *err);
+int tx_stuff(int device, int64_t rows, int w, int factor, double scale, const void *in, void *out, std::string *err);
 int rx_decimate(int device, int64_t N, int ncols, int SpSin, int decFactor, const void *in, void *out, int32_t *sampDelay,
                 std::string *err);
 // engine_metrics.hip (arguments already checked by ssf_api.hip)
