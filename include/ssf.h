@@ -41,6 +41,9 @@
  *   ssf_modulate_optical                 pm, mzm, iqm                     optic/models/devices.py:56-220
  *   ssf_awgn                             awgn                             optic/models/channels.py:522-565
  *   ssf_upsample                         upsample, voa                    optic/dsp/core.py:395-432, devices.py:263-286
+ *   ssf_mlse                             mlse                             optic/comm/modulation.py:582-680
+ *   ssf_detector                         detector                         optic/comm/modulation.py:412-481
+ *   ssf_autocorr                         autocorr                         optic/dsp/core.py:1194-1227
  *   ssf_device_copy_bandwidth            (no reference equivalent) measured memory ceiling
  *   ssf_set_profiling / ssf_get_kernel_times   time.time() pairs around calls in
  *                                        examples/benchmarck_GPU_processing.ipynb:389-395
@@ -735,6 +738,53 @@ typedef struct {
 } ssf_siso_params;
 int  ssf_siso_eq(int device, ssf_siso_params *params, const double *const_tab, void *coef_inout, const void *x, const void *ref,
                  void *sig_out, double *mse_out);
+
+/* ---- sequence and symbol detection on the device (optic/comm/modulation.py:412-481 detector, 582-680 mlse) and the
+ * autocorrelation behind estimateWhiteningFilter (optic/dsp/core.py:1194-1227).
+ *
+ * ssf_mlse: maximum-likelihood sequence estimation by the Viterbi algorithm over the impulse response h, one independent sequence
+ * per column.  All path metrics start at zero; the branch metric is |y[n] - expected|^2 with the expected outputs summed in the
+ * reference's order; the survivor is the candidate with the smallest metric, the lowest predecessor state among equal ones; the
+ * final state is the lowest-index minimum.  Arithmetic is double.
+ *   y             (n, cols) row-major, float64 (SSF_M_F64) or complex128 (SSF_M_C128), host or device; never written
+ *   h             taps (re, im) pairs, host;  const_tab: M (re, im) pairs, host (imaginary parts are ignored for float64 y)
+ *   out           (n, cols) of y's type, host or device: const_tab[k] of the decided symbols
+ *   final_metric  cols float64, host: the smallest path metric after the last step
+ * One workgroup per column runs the forward pass with one lane per state; the traceback is three launches (per-chunk end-state
+ * maps, their composition, one walker per chunk).  The host waits once.  On return states, kernel, chunk and survivor_bytes say
+ * what ran; with timing = 1 fwd_ms and tb_ms hold the device time of the forward pass and of the traceback.
+ * Limits: 1 <= M <= 64, 1 <= taps <= 11, M^(taps - 1) <= 1024, 1 <= cols <= 64, n >= 1, survivor memory (cols rows of n
+ * max(4, states rounded up to 4) bytes, each column rounded up to 16) at most 2^31 bytes. */
+typedef struct {
+    int64_t n;                    /* symbols per column */
+    int32_t cols;
+    int32_t dtype;                /* SSF_M_F64 or SSF_M_C128 */
+    int32_t M, taps;
+    int32_t timing;               /* 1: measure fwd_ms and tb_ms with events */
+    int32_t states;               /* out: M^(taps - 1) */
+    int32_t kernel;               /* out: 0 the one-wavefront forward kernel, 1 the one of several wavefronts */
+    int32_t chunk;                /* out: steps per survivor chunk */
+    int64_t survivor_bytes;       /* out */
+    double  fwd_ms, tb_ms;        /* out */
+} ssf_mlse_params;
+int  ssf_mlse(int device, ssf_mlse_params *params, const double *h, const double *const_tab, const void *y, void *out,
+              double *final_metric);
+
+/* ssf_detector: symbol-by-symbol decisions.  rule SSF_DET_ML: the first index of the smallest |r - c|^2; SSF_DET_MAP: the first
+ * index of the largest -|r - c|^2 / sigma2 + logpx.
+ *   r           n values of `dtype` (SSF_M_F64 or SSF_M_C128), host or device; never written
+ *   const_tab   M (re, im) pairs, host;  logpx: M float64, host: the log priors (-inf for a zero prior); may be NULL for SSF_DET_ML
+ *   decided     n values of r's type, host or device;  ind: n int64, host or device
+ * Limits: 1 <= M <= 64, n >= 1, sigma2 > 0 for SSF_DET_MAP. */
+typedef enum { SSF_DET_ML = 0, SSF_DET_MAP = 1 } ssf_detector_rule;
+int  ssf_detector(int device, int64_t n, int32_t dtype, int32_t M, int32_t rule, double sigma2, const double *const_tab,
+                  const double *logpx, const void *r, void *decided, int64_t *ind);
+
+/* ssf_autocorr: r_out[k] = sum_{i >= k} x[i] x[i - k] / (n - k) for k = 0 .. nTaps - 1, one launch for all lags and a fixed-order
+ * sum of the workgroups' partials.
+ *   x           n float64, host or device; never written;  r_out: nTaps float64, host
+ * Limits: 1 <= nTaps <= 256, nTaps <= n. */
+int  ssf_autocorr(int device, int64_t n, int32_t nTaps, const void *x, double *r_out);
 
 /* ---- soft-decision FEC on the device: the soft demapper and the LDPC belief-propagation decoder that end the reference's chain
  * (optic/comm/metrics.py:198-239 calcLLR; optic/comm/fec.py:347-758 sumProductAlgorithm, minSumAlgorithm, decodeLDPC).

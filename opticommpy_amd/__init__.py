@@ -44,6 +44,8 @@ from .ofdm import calcSymbolRate, demodulateOFDM, hermit, modulateOFDM, zeroPad 
 from .perturbation import calcNLINperturbation, calcNLINperturbationSimplified, calcPertCoeffMatrix, perturbationNLIN  # noqa: F401
 from . import imddtx  # noqa: F401
 from .imddtx import awgn, bitSource, iqm, mzm, pamTransmitter, pm, prbsGenerator, symbolSource, upsample, voa  # noqa: F401
+from . import seqdet  # noqa: F401
+from .seqdet import autocorr, detector, estimateWhiteningFilter, levinson, mlse  # noqa: F401
 from . import clock  # noqa: F401
 from .clock import (  # noqa: F401
     adc, calcClockDrift, clockSamplingInterp, dac, gardnerClockRecovery, gardnerTED, gardnerTEDnyquist, interpolator, quantizer, resample,
@@ -59,4 +61,5 @@ __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMa
            "calcPertCoeffMatrix", "calcNLINperturbation", "calcNLINperturbationSimplified", "perturbationNLIN",
            "clockSamplingInterp", "quantizer", "resample", "adc", "dac", "gardnerClockRecovery", "calcClockDrift", "gardnerTED",
            "gardnerTEDnyquist", "interpolator",
-           "pamTransmitter", "mzm", "pm", "iqm", "voa", "upsample", "awgn", "bitSource", "prbsGenerator", "symbolSource"]
+           "pamTransmitter", "mzm", "pm", "iqm", "voa", "upsample", "awgn", "bitSource", "prbsGenerator", "symbolSource",
+           "mlse", "detector", "autocorr", "levinson", "estimateWhiteningFilter"]

@@ -255,6 +255,27 @@ SISO_CHUNK = 64            # symbols the serial kernel stages per chunk (kChunk)
 SISO_TILE = 256            # symbols per workgroup of the frozen kernel (kTile)
 
 
+class MlseParams(C.Structure):
+    """ssf_mlse_params (include/ssf.h)."""
+    _fields_ = [("n", C.c_int64), ("cols", C.c_int32), ("dtype", C.c_int32), ("M", C.c_int32), ("taps", C.c_int32), ("timing", C.c_int32),
+                ("states", C.c_int32), ("kernel", C.c_int32), ("chunk", C.c_int32), ("survivor_bytes", C.c_int64), ("fwd_ms", C.c_double),
+                ("tb_ms", C.c_double)]
+
+
+SEQDET_MAX_M = 64          # constellation points of mlse and detector (seqdet_kernels.h: kMaxM)
+SEQDET_MAX_STATES = 1024   # trellis states M ** (taps - 1) (kMaxStates)
+SEQDET_MAX_TAPS = 11       # (kMaxTaps)
+SEQDET_MAX_COLS = 64       # (kMaxCols)
+SEQDET_SURV_CHUNK = 32     # T: steps per survivor chunk (kSurvChunk)
+SEQDET_STAGE_CHUNK = 256   # C: samples of y staged at a time (kStageChunk)
+SEQDET_MAX_SURVIVOR_BYTES = 1 << 31
+SEQDET_KERNELS = ("forward_wave64", "forward_multiwave")                                     # ssf_mlse_params.kernel
+SEQDET_RULES = {"ML": 0, "MAP": 1}                                                           # ssf_detector_rule
+SEQDET_DET_BLOCK = 256     # detector: symbols per workgroup (kDetBlock)
+SEQDET_AC_MAX_TAPS = 256   # autocorr (kAcMaxTaps)
+SEQDET_AC_TILE = 4096      # samples per tile of autocorr (kAcTile)
+
+
 def siso_slots(ncoef):
     """Coefficient slots per lane the serial kernel is compiled for (siso_kernels.h: slots_for)."""
     r = (ncoef + 63) // 64
@@ -354,6 +375,11 @@ SYMBOLS = {
                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssf_siso_eq": (C.c_int, [C.c_int, C.POINTER(SisoParams), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p]),
+    "ssf_mlse": (C.c_int, [C.c_int, C.POINTER(MlseParams), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p, C.c_void_p,
+                           C.POINTER(C.c_double)]),
+    "ssf_detector": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_autocorr": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     "ssf_calc_llr": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "ssf_ldpc_graph_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

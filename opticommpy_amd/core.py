@@ -5,5 +5,6 @@ from .imddtx import upsample  # noqa: F401
 from .metrics import anorm, pnorm, signalPower  # noqa: F401
 from .models import blockwiseFFTConv  # noqa: F401
 from .rx import decimate, delaySignal, firFilter, iqMixing, lowPassFIR  # noqa: F401
+from .seqdet import autocorr, estimateWhiteningFilter, levinson  # noqa: F401
 from .sync import finddelay, symbolSync  # noqa: F401
 from .wdm_tx import phaseNoise, pulseShape  # noqa: F401

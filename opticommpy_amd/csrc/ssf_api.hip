@@ -958,6 +958,52 @@ int ssf_siso_eq(int device, ssf_siso_params *p, const double *const_tab, void *c
     return rc ? set_err(rc, "ssf_siso_eq: " + err) : SSF_OK;
 }
 
+// ---- mlse, detector, autocorr (engine_seqdet.hip): every check comes before the first allocation or launch
+int ssf_mlse(int device, ssf_mlse_params *p, const double *h, const double *const_tab, const void *y, void *out, double *final_metric) {
+    if (!p || !h || !const_tab || !y || !out || !final_metric) return set_err(SSF_ERR_BAD_ARG, "ssf_mlse: NULL argument");
+    if (p->dtype != SSF_M_F64 && p->dtype != SSF_M_C128) return set_err(SSF_ERR_UNSUPPORTED, "ssf_mlse: float64 or complex128 arrays");
+    if (p->M < 1 || p->M > 64) return set_err(SSF_ERR_BAD_ARG, "ssf_mlse: M must be 1 .. 64");
+    if (p->taps < 1 || p->taps > 11) return set_err(SSF_ERR_BAD_ARG, "ssf_mlse: 1 .. 11 taps");
+    int64_t states = 1;
+    for (int i = 1; i < p->taps && states <= 1024; ++i) states *= p->M;
+    if (states > 1024) return set_err(SSF_ERR_BAD_ARG, "ssf_mlse: more than 1024 states");
+    if (p->cols < 1 || p->cols > 64) return set_err(SSF_ERR_BAD_ARG, "ssf_mlse: 1 .. 64 columns");
+    if (p->n < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_mlse: n must be at least 1");
+    if (p->n > ((int64_t)1 << 31)) return set_err(SSF_ERR_BAD_ARG, "ssf_mlse: survivor memory above 2^31 bytes");
+    const int64_t bytes = ssf::mlse_survivor_bytes(p->n, p->cols, p->M, p->taps);
+    if (bytes > ((int64_t)1 << 31))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_mlse: survivor memory of " + std::to_string(bytes) + " bytes is above 2^31 bytes");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::mlse_run(device, p, h, const_tab, y, out, final_metric, &err);
+    return rc ? set_err(rc, "ssf_mlse: " + err) : SSF_OK;
+}
+
+int ssf_detector(int device, int64_t n, int32_t dtype, int32_t M, int32_t rule, double sigma2, const double *const_tab, const double *logpx,
+                 const void *r, void *decided, int64_t *ind) {
+    if (!const_tab || !r || !decided || !ind) return set_err(SSF_ERR_BAD_ARG, "ssf_detector: NULL argument");
+    if (rule != SSF_DET_ML && rule != SSF_DET_MAP) return set_err(SSF_ERR_BAD_ARG, "ssf_detector: unknown rule");
+    if (rule == SSF_DET_MAP && !logpx) return set_err(SSF_ERR_BAD_ARG, "ssf_detector: NULL argument");
+    if (dtype != SSF_M_F64 && dtype != SSF_M_C128) return set_err(SSF_ERR_UNSUPPORTED, "ssf_detector: float64 or complex128 arrays");
+    if (M < 1 || M > 64) return set_err(SSF_ERR_BAD_ARG, "ssf_detector: M must be 1 .. 64");
+    if (n < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_detector: n must be at least 1");
+    if (rule == SSF_DET_MAP && !(sigma2 > 0)) return set_err(SSF_ERR_BAD_ARG, "ssf_detector: sigma2 must be positive");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::detector_run(device, n, dtype, M, rule, sigma2, const_tab, logpx, r, decided, ind, &err);
+    return rc ? set_err(rc, "ssf_detector: " + err) : SSF_OK;
+}
+
+int ssf_autocorr(int device, int64_t n, int32_t nTaps, const void *x, double *r_out) {
+    if (!x || !r_out) return set_err(SSF_ERR_BAD_ARG, "ssf_autocorr: NULL argument");
+    if (nTaps < 1 || nTaps > 256) return set_err(SSF_ERR_BAD_ARG, "ssf_autocorr: nTaps must be 1 .. 256");
+    if (n < nTaps) return set_err(SSF_ERR_BAD_ARG, "ssf_autocorr: nTaps exceeds n");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::autocorr_run(device, n, nTaps, x, r_out, &err);
+    return rc ? set_err(rc, "ssf_autocorr: " + err) : SSF_OK;
+}
+
 // ---- soft-decision FEC (engine_fec.hip): every check comes before the first allocation, upload or launch
 int ssf_calc_llr(int device, int64_t n, int32_t dtype, int32_t M, double sigma2, const double *const_tab, const int32_t *bitmap,
                  const double *px, const void *x, double *llr_out) {

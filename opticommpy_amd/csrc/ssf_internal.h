@@ -192,6 +192,13 @@ int eq_run(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const
 // engine_siso.hip (arguments already checked by ssf_api.hip)
 int siso_run(int device, ssf_siso_params *p, const double *table, void *coef_inout, const void *x, const void *ref, void *sig_out,
              double *mse_out, std::string *err);
+// engine_seqdet.hip (arguments already checked by ssf_api.hip)
+int64_t mlse_survivor_bytes(int64_t n, int cols, int M, int taps);
+int mlse_run(int device, ssf_mlse_params *p, const double *h, const double *const_tab, const void *y, void *out, double *final_metric,
+             std::string *err);
+int detector_run(int device, int64_t n, int dtype, int M, int rule, double sigma2, const double *const_tab, const double *logpx, const void *r,
+                 void *decided, int64_t *ind, std::string *err);
+int autocorr_run(int device, int64_t n, int nTaps, const void *x, double *r_out, std::string *err);
 // engine_fec.hip (arguments already checked by ssf_api.hip)
 int fec_calc_llr(int device, int64_t n, int dtype, int M, double sigma2, const double *table, const int32_t *bitmap, const double *px,
                  const void *x, double *llr_out, std::string *err);
