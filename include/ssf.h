@@ -44,6 +44,9 @@
  *   ssf_mlse                             mlse                             optic/comm/modulation.py:582-680
  *   ssf_detector                         detector                         optic/comm/modulation.py:412-481
  *   ssf_autocorr                         autocorr                         optic/dsp/core.py:1194-1227
+ *   ssf_sync_tile / ssf_sync_extract / ssf_real_part / ssf_copy_columns   the glue of syncDataSequences   optic/dsp/synchronization.py:30-170
+ *   ssf_moving_average                   movingAverage                    optic/dsp/core.py:829-880
+ *   ssf_bert                             bert                             optic/comm/metrics.py:37-105
  *   ssf_device_copy_bandwidth            (no reference equivalent) measured memory ceiling
  *   ssf_set_profiling / ssf_get_kernel_times   time.time() pairs around calls in
  *                                        examples/benchmarck_GPU_processing.ipynb:389-395
@@ -785,6 +788,40 @@ int  ssf_detector(int device, int64_t n, int32_t dtype, int32_t M, int32_t rule,
  *   x           n float64, host or device; never written;  r_out: nTaps float64, host
  * Limits: 1 <= nTaps <= 256, nTaps <= n. */
 int  ssf_autocorr(int device, int64_t n, int32_t nTaps, const void *x, double *r_out);
+
+/* ---- the glue of syncDataSequences, movingAverage and bert (optic/dsp/synchronization.py:30-170, optic/dsp/core.py:829-880,
+ * optic/comm/metrics.py:37-105; engine_syncdata.hip).  Array arguments are host or device pointers unless said otherwise; inputs
+ * are never written; no atomics: a second call repeats the first bit for bit.
+ *
+ * ssf_sync_tile: tx_out[i, m] = tx[(i / SpS) mod n_tx, m] where i mod SpS == 0, else 0, and rx_out[i, m] = rx[i, m] for i < n_rx,
+ * else 0; both (n_pad, nModes) complex128, rx and tx of any of complex128 / complex64 / float64.
+ * Limits: 1 <= nModes <= 8, SpS >= 1, n_rx >= 1, n_tx >= 1, n_rx <= n_pad <= 2^31. */
+typedef struct {
+    int64_t n_rx, n_tx, n_pad;
+    int32_t nModes, SpS;
+    int32_t rx_dtype, tx_dtype;   /* SSF_M_C128, SSF_M_C64 or SSF_M_F64 */
+} ssf_sync_tile_params;
+int  ssf_sync_tile(int device, const ssf_sync_tile_params *params, const void *rx, const void *tx, void *rx_out, void *tx_out);
+/* ssf_sync_extract: per column of x ((n, nModes) complex128) the non-zero samples in their order, written from row 0 of out
+ * ((n_out, nModes) of out_dtype: SSF_M_C128, or SSF_M_F64 for the real parts), zeros below them; with `normalize` each column is
+ * divided by the root mean square of its kept samples.  kept: nModes int64, host.  Samples whose rank is n_out or more are dropped.
+ * Limits: 1 <= nModes <= 8, 1 <= n <= 2^31, n_out >= 1. */
+int  ssf_sync_extract(int device, int64_t n, int32_t nModes, int64_t n_out, int32_t out_dtype, int32_t normalize, const void *x, void *out,
+                      int64_t *kept);
+/* ssf_real_part: out[i] = Re x[i]; x count complex128, out count float64 */
+int  ssf_real_part(int device, int64_t count, const void *x, void *out);
+/* ssf_copy_columns: dst[i, dst_first + j] = src[i, src_first + j] for i < n, j < width; src (n, src_cols) and dst (n, dst_cols)
+ * complex128 device arrays, not the same one; the other columns of dst are left as they are.  How syncDataSequences hands decimate
+ * at most six columns at a time and puts the results side by side. */
+int  ssf_copy_columns(int device, int64_t n, int32_t width, int32_t src_cols, int32_t src_first, int32_t dst_cols, int32_t dst_first,
+                      const void *src, void *dst);
+/* ssf_moving_average: out[i, c] = (1 / N) sum_{j = i - N/2}^{i + (N-1)/2} x[j, c], zeros outside [0, n); x (n, cols) of complex128,
+ * complex64 or float64; out float64 for float64 x and complex128 otherwise.  Limits: 2 <= N <= 2048, n >= 1, 1 <= cols <= 65535. */
+int  ssf_moving_average(int device, int64_t n, int32_t cols, int32_t N, int32_t dtype, const void *x, void *out);
+/* ssf_bert: the statistics of bert over n float64 samples and n bits (one byte each: a bit is 1 where its byte equals 1, any other value counts as 0).  scal_out: 10 float64, host:
+ * n1, n0, I1, I0, std1, std0 (population), Id, Q, the number of decisions (Irx > Id) that differ from the bit, 0.  With an empty
+ * class the call succeeds and the caller reads n1 or n0 == 0 (the other values are then not numbers).  Limit: n >= 1. */
+int  ssf_bert(int device, int64_t n, const void *irx, const void *bits, double *scal_out);
 
 /* ---- soft-decision FEC on the device: the soft demapper and the LDPC belief-propagation decoder that end the reference's chain
  * (optic/comm/metrics.py:198-239 calcLLR; optic/comm/fec.py:347-758 sumProductAlgorithm, minSumAlgorithm, decodeLDPC).

@@ -16,6 +16,10 @@ The front of the direct-detection notebooks is there too (``opticommpy_amd.imddt
 ``mzm`` and ``iqm``, ``voa``, ``upsample`` and the ``awgn`` channel on numpy arrays and ``DeviceArray``s, and the host-side sources
 ``bitSource``, ``prbsGenerator`` and ``symbolSource``; also importable from ``opticommpy_amd.tx``, ``.devices``, ``.channels``,
 ``.core`` and ``.sources``, as in the reference.
+
+``syncDataSequences`` (``opticommpy_amd.synchronization``) aligns the transmitted sequence to a delayed, repeated received copy and
+returns the reference symbols of the equalizers; ``movingAverage`` (also in ``.core``) and ``bert``, ``theoryBER``, ``Qfunc`` (also
+in ``.metrics``) complete the names the direct-detection notebooks import.
 """
 from .utils import parameters  # noqa: F401
 from .models import (  # noqa: F401
@@ -46,6 +50,8 @@ from . import imddtx  # noqa: F401
 from .imddtx import awgn, bitSource, iqm, mzm, pamTransmitter, pm, prbsGenerator, symbolSource, upsample, voa  # noqa: F401
 from . import seqdet  # noqa: F401
 from .seqdet import autocorr, detector, estimateWhiteningFilter, levinson, mlse  # noqa: F401
+from . import synchronization  # noqa: F401
+from .synchronization import Qfunc, bert, movingAverage, syncDataSequences, theoryBER  # noqa: F401
 from . import clock  # noqa: F401
 from .clock import (  # noqa: F401
     adc, calcClockDrift, clockSamplingInterp, dac, gardnerClockRecovery, gardnerTED, gardnerTEDnyquist, interpolator, quantizer, resample,
@@ -62,4 +68,5 @@ __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMa
            "clockSamplingInterp", "quantizer", "resample", "adc", "dac", "gardnerClockRecovery", "calcClockDrift", "gardnerTED",
            "gardnerTEDnyquist", "interpolator",
            "pamTransmitter", "mzm", "pm", "iqm", "voa", "upsample", "awgn", "bitSource", "prbsGenerator", "symbolSource",
-           "mlse", "detector", "autocorr", "levinson", "estimateWhiteningFilter"]
+           "mlse", "detector", "autocorr", "levinson", "estimateWhiteningFilter",
+           "syncDataSequences", "movingAverage", "bert", "theoryBER", "Qfunc"]

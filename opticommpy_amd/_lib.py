@@ -276,6 +276,19 @@ SEQDET_AC_MAX_TAPS = 256   # autocorr (kAcMaxTaps)
 SEQDET_AC_TILE = 4096      # samples per tile of autocorr (kAcTile)
 
 
+class SyncTileParams(C.Structure):
+    """ssf_sync_tile_params (include/ssf.h)."""
+    _fields_ = [("n_rx", C.c_int64), ("n_tx", C.c_int64), ("n_pad", C.c_int64), ("nModes", C.c_int32), ("SpS", C.c_int32),
+                ("rx_dtype", C.c_int32), ("tx_dtype", C.c_int32)]
+
+
+SYNCDATA_BLOCK = 256       # lanes per workgroup of the syncDataSequences / movingAverage / bert kernels (syncdata_kernels.h: kBlock)
+SYNCDATA_SPAN = 1024       # B: rows of a column one workgroup of the extraction scans (kSpan)
+SYNCDATA_MA_TILE = 1024    # T: outputs of a column per workgroup of the windowed mean (kMaTile)
+SYNCDATA_MA_MAX_N = 2048   # longest window (kMaMaxN)
+SYNCDATA_BERT_BLOCKS = 1024                                                                  # most workgroups of bert's passes
+
+
 def siso_slots(ncoef):
     """Coefficient slots per lane the serial kernel is compiled for (siso_kernels.h: slots_for)."""
     r = (ncoef + 63) // 64
@@ -380,6 +393,13 @@ SYMBOLS = {
     "ssf_detector": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssf_autocorr": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
+    "ssf_sync_tile": (C.c_int, [C.c_int, C.POINTER(SyncTileParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_sync_extract": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                   C.POINTER(C.c_int64)]),
+    "ssf_real_part": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ssf_copy_columns": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ssf_moving_average": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ssf_bert": (C.c_int, [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "ssf_calc_llr": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_int32),
                                C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
     "ssf_ldpc_graph_create": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),

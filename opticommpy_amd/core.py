@@ -7,4 +7,5 @@ from .models import blockwiseFFTConv  # noqa: F401
 from .rx import decimate, delaySignal, firFilter, iqMixing, lowPassFIR  # noqa: F401
 from .seqdet import autocorr, estimateWhiteningFilter, levinson  # noqa: F401
 from .sync import finddelay, symbolSync  # noqa: F401
+from .synchronization import movingAverage  # noqa: F401
 from .wdm_tx import phaseNoise, pulseShape  # noqa: F401

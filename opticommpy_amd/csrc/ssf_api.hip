@@ -1004,6 +1004,74 @@ int ssf_autocorr(int device, int64_t n, int32_t nTaps, const void *x, double *r_
     return rc ? set_err(rc, "ssf_autocorr: " + err) : SSF_OK;
 }
 
+// ---- syncDataSequences' glue, movingAverage, bert (engine_syncdata.hip): every check comes before the first allocation or launch
+int ssf_sync_tile(int device, const ssf_sync_tile_params *p, const void *rx, const void *tx, void *rx_out, void *tx_out) {
+    if (!p || !rx || !tx || !rx_out || !tx_out) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_tile: NULL argument");
+    if (p->nModes < 1 || p->nModes > 8) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_tile: nModes must be 1 .. 8");
+    if (p->SpS < 1 || p->n_rx < 1 || p->n_tx < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_tile: SpS, n_rx and n_tx must be at least 1");
+    if (p->n_pad < p->n_rx || p->n_pad > (1LL << 31)) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_tile: n_rx <= n_pad <= 2^31");
+    for (int32_t d : {p->rx_dtype, p->tx_dtype})
+        if (d != SSF_M_C128 && d != SSF_M_C64 && d != SSF_M_F64) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_tile: dtype must be complex128, complex64 or float64");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::syncdata_tile(device, p, rx, tx, rx_out, tx_out, &err);
+    return rc ? set_err(rc, "ssf_sync_tile: " + err) : SSF_OK;
+}
+
+int ssf_sync_extract(int device, int64_t n, int32_t nModes, int64_t n_out, int32_t out_dtype, int32_t normalize, const void *x, void *out,
+                     int64_t *kept) {
+    if (!x || !out || !kept) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_extract: NULL argument");
+    if (nModes < 1 || nModes > 8) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_extract: nModes must be 1 .. 8");
+    if (n < 1 || n > (1LL << 31) || n_out < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_extract: 1 <= n <= 2^31 and n_out >= 1");
+    if (out_dtype != SSF_M_C128 && out_dtype != SSF_M_F64) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_extract: out_dtype must be complex128 or float64");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::syncdata_extract(device, n, nModes, n_out, out_dtype, normalize != 0, x, out, kept, &err);
+    return rc ? set_err(rc, "ssf_sync_extract: " + err) : SSF_OK;
+}
+
+int ssf_real_part(int device, int64_t count, const void *x, void *out) {
+    if (!x || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_real_part: NULL argument");
+    if (count < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_real_part: count must be at least 1");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::syncdata_real_part(device, count, x, out, &err);
+    return rc ? set_err(rc, "ssf_real_part: " + err) : SSF_OK;
+}
+
+int ssf_copy_columns(int device, int64_t n, int32_t width, int32_t src_cols, int32_t src_first, int32_t dst_cols, int32_t dst_first, const void *src,
+                     void *dst) {
+    if (!src || !dst) return set_err(SSF_ERR_BAD_ARG, "ssf_copy_columns: NULL argument");
+    if (n < 1 || n > (1LL << 40) || width < 1 || src_first < 0 || dst_first < 0 || src_first + (int64_t)width > src_cols || dst_first + (int64_t)width > dst_cols)
+        return set_err(SSF_ERR_BAD_ARG, "ssf_copy_columns: n >= 1 and the block of columns inside both arrays");
+    if (src == dst) return set_err(SSF_ERR_BAD_ARG, "ssf_copy_columns: src and dst must be different arrays");
+    if (!ssf::on_device(src) || !ssf::on_device(dst)) return set_err(SSF_ERR_BAD_ARG, "ssf_copy_columns: src and dst are device arrays");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::syncdata_copy_columns(device, n, width, src_cols, src_first, dst_cols, dst_first, src, dst, &err);
+    return rc ? set_err(rc, "ssf_copy_columns: " + err) : SSF_OK;
+}
+
+int ssf_moving_average(int device, int64_t n, int32_t cols, int32_t N, int32_t dtype, const void *x, void *out) {
+    if (!x || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_moving_average: NULL argument");
+    if (N < 2 || N > 2048) return set_err(SSF_ERR_BAD_ARG, "ssf_moving_average: N must be 2 .. 2048");
+    if (n < 1 || cols < 1 || cols > 65535) return set_err(SSF_ERR_BAD_ARG, "ssf_moving_average: n >= 1 and 1 <= cols <= 65535");
+    if (dtype != SSF_M_C128 && dtype != SSF_M_C64 && dtype != SSF_M_F64) return set_err(SSF_ERR_BAD_ARG, "ssf_moving_average: dtype must be complex128, complex64 or float64");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::syncdata_moving_average(device, n, cols, N, dtype, x, out, &err);
+    return rc ? set_err(rc, "ssf_moving_average: " + err) : SSF_OK;
+}
+
+int ssf_bert(int device, int64_t n, const void *irx, const void *bits, double *scal_out) {
+    if (!irx || !bits || !scal_out) return set_err(SSF_ERR_BAD_ARG, "ssf_bert: NULL argument");
+    if (n < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_bert: n must be at least 1");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::syncdata_bert(device, n, irx, bits, scal_out, &err);
+    return rc ? set_err(rc, "ssf_bert: " + err) : SSF_OK;
+}
+
 // ---- soft-decision FEC (engine_fec.hip): every check comes before the first allocation, upload or launch
 int ssf_calc_llr(int device, int64_t n, int32_t dtype, int32_t M, double sigma2, const double *const_tab, const int32_t *bitmap,
                  const double *px, const void *x, double *llr_out) {

@@ -199,6 +199,15 @@ int mlse_run(int device, ssf_mlse_params *p, const double *h, const double *cons
 int detector_run(int device, int64_t n, int dtype, int M, int rule, double sigma2, const double *const_tab, const double *logpx, const void *r,
                  void *decided, int64_t *ind, std::string *err);
 int autocorr_run(int device, int64_t n, int nTaps, const void *x, double *r_out, std::string *err);
+// engine_syncdata.hip (arguments already checked by ssf_api.hip)
+int syncdata_tile(int device, const ssf_sync_tile_params *p, const void *rx, const void *tx, void *rx_out, void *tx_out, std::string *err);
+int syncdata_real_part(int device, int64_t count, const void *x, void *out, std::string *err);
+int syncdata_copy_columns(int device, int64_t n, int width, int src_cols, int src_first, int dst_cols, int dst_first, const void *src, void *dst,
+                          std::string *err);
+int syncdata_extract(int device, int64_t n, int modes, int64_t n_out, int out_dtype, int normalize, const void *x, void *out, int64_t *kept,
+                     std::string *err);
+int syncdata_moving_average(int device, int64_t n, int cols, int N, int dtype, const void *x, void *out, std::string *err);
+int syncdata_bert(int device, int64_t n, const void *irx, const void *bits, double *scal_out, std::string *err);
 // engine_fec.hip (arguments already checked by ssf_api.hip)
 int fec_calc_llr(int device, int64_t n, int dtype, int M, double sigma2, const double *table, const int32_t *bitmap, const double *px,
                  const void *x, double *llr_out, std::string *err);

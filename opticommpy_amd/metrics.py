@@ -28,9 +28,11 @@ import numpy as np
 
 from . import _lib
 from . import device as _dev
+from .synchronization import Qfunc, bert, theoryBER  # noqa: F401  (optic/comm/metrics.py names them; they live with syncDataSequences)
 from .wdm_tx import grayMapping
 
-__all__ = ["fastBERcalc", "monteCarloGMI", "monteCarloMI", "calcEVM", "demodulateGray", "pnorm", "anorm", "signalPower", "metrics"]
+__all__ = ["fastBERcalc", "monteCarloGMI", "monteCarloMI", "calcEVM", "demodulateGray", "pnorm", "anorm", "signalPower", "metrics",
+           "bert", "theoryBER", "Qfunc"]
 
 _NAMES = ("BER", "SER", "SNR", "GMI", "NGMI", "MI", "EVM")
 
