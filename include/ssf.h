@@ -1052,6 +1052,65 @@ int  ssf_gardner(int device, const ssf_gardner_params *params, const void *x, vo
  * whole array (per_column == 0, the reference's 2-D call) or over the column (the reference's call per 1-D column). */
 int  ssf_clock_drift(int device, int64_t n, int32_t ncols, int32_t per_column, const double *t, double *ppm_out);
 
+/* ---- the general array layer of DeviceArray (engine_array.hip, array_kernels.h): what stands between two stages of a notebook --
+ * indexing, transposes, concatenation, element-wise arithmetic, dtype conversion, reductions -- with numpy as the definition.
+ * Array data (src, dst, a, x, out, and b unless it is a row) are DEVICE pointers: a host pointer there is SSF_ERR_BAD_ARG.  The
+ * small operands -- the index of ssf_array_take, a row operand, the centre of a reduction, the fill value -- may be host memory;
+ * reduction results are written to host memory.  No entry point writes its operands or works in place.  A call of zero elements
+ * returns SSF_OK without a launch.  Every entry point has finished its work when it returns: a result may be handed to any other
+ * engine's stream.  dtype arguments are ssf_metrics_dtype.  Arithmetic is double, single-precision data are widened on load and
+ * rounded once on store; a real operand beside a complex one is promoted to (re, +0) as numpy's casts do. */
+#define SSF_ARRAY_MAX_DIM 4
+typedef struct {
+    int32_t ndim;                 /* 0 .. SSF_ARRAY_MAX_DIM */
+    int32_t itemsize;             /* 1, 2, 4, 8 or 16 bytes */
+    int64_t offset;               /* of element (0, 0, ..) from the pointer, in elements */
+    int64_t extent;               /* elements of the allocation behind the pointer: every element reached lies in [0, extent) */
+    int64_t shape[SSF_ARRAY_MAX_DIM];
+    int64_t stride[SSF_ARRAY_MAX_DIM];    /* in elements, any sign */
+} ssf_array_desc;
+/* dst[dst_desc] = src[src_desc]: same ndim, shape and itemsize on both sides, elements taken in C order of the shape.  Serves
+ * slices with any step, integer indices, concatenate and stack.  Contiguous, 16-byte aligned sides move 16 bytes per lane. */
+int  ssf_array_copy(int device, const ssf_array_desc *src_desc, const void *src, const ssf_array_desc *dst_desc, void *dst);
+/* dst (n_idx, inner) = src (n_src, inner)[idx]: idx holds n_idx int32 or int64 (idx_itemsize 4 or 8), host or device.  Negative
+ * entries wrap; an entry still out of range is CLAMPED to the first or last row (the host checks what it can see). */
+int  ssf_array_take(int device, int64_t n_src, int64_t n_idx, int64_t inner, int32_t itemsize, int32_t idx_itemsize, const void *idx,
+                    const void *src, void *dst);
+/* dst (cols, rows) = src (rows, cols) transposed, through a padded LDS tile */
+int  ssf_array_transpose(int device, int64_t rows, int64_t cols, int32_t itemsize, const void *src, void *dst);
+/* dst[0 .. count) = the itemsize bytes at value (host) */
+int  ssf_array_fill(int device, int64_t count, int32_t itemsize, const void *value, void *dst);
+enum ssf_array_binary_op { SSF_ARRAY_ADD = 0, SSF_ARRAY_SUB = 1, SSF_ARRAY_MUL = 2, SSF_ARRAY_DIV = 3 };
+/* how the second operand meets the first: element for element; one value (scalar_re, scalar_im; b is ignored); a row of `inner`
+ * values along the last axis (host or device); a column: one value per `inner` consecutive elements of a (device) */
+enum ssf_array_bcast { SSF_ARRAY_SAME = 0, SSF_ARRAY_SCALAR = 1, SSF_ARRAY_ROW = 2, SSF_ARRAY_COLUMN = 3 };
+typedef struct {
+    int32_t op;                   /* ssf_array_binary_op */
+    int32_t swap;                 /* 1: b op a (the reflected operators) */
+    int32_t a_dtype, b_dtype, out_dtype;      /* out_dtype is complex exactly if a_dtype or b_dtype is */
+    int32_t kind;                 /* ssf_array_bcast */
+    int64_t count;                /* elements of a and of out */
+    int64_t inner;                /* SSF_ARRAY_ROW, SSF_ARRAY_COLUMN: divides count */
+    double  scalar_re, scalar_im; /* SSF_ARRAY_SCALAR, taken as of b_dtype's kind */
+} ssf_array_binary_params;
+/* out = a op b.  Complex products are re = ar br - ai bi, im = ar bi + ai br; complex quotients are Smith's form, as numpy's loop. */
+int  ssf_array_binary(int device, const ssf_array_binary_params *params, const void *a, const void *b, void *out);
+/* REAL, IMAG, ABS, ABS2 (re^2 + im^2) and ANGLE give a real out_dtype; NEG, CONJ and EXP keep the kind; SQRT is for real arrays;
+ * CONVERT goes between any two dtypes except from complex to real.  ABS of a complex value is hypot: finite where the value is. */
+enum ssf_array_unary_op { SSF_ARRAY_NEG = 0, SSF_ARRAY_CONJ = 1, SSF_ARRAY_REAL = 2, SSF_ARRAY_IMAG = 3, SSF_ARRAY_ABS = 4,
+                          SSF_ARRAY_ABS2 = 5, SSF_ARRAY_ANGLE = 6, SSF_ARRAY_EXP = 7, SSF_ARRAY_SQRT = 8, SSF_ARRAY_CONVERT = 9 };
+int  ssf_array_unary(int device, int32_t op, int32_t in_dtype, int32_t out_dtype, int64_t count, const void *x, void *out);
+/* per column of x (rows, cols) over its rows (the whole array: cols = 1), accumulated in double:
+ * SUM -> out[2 c], out[2 c + 1] = the sums of the real and imaginary parts; SUMSQDEV -> out[2 c] = sum |x - centre[c]|^2 with
+ * centre (cols, 2) doubles; MIN / MAX (real dtypes) -> out[c] and arg_out[c], numpy's rule: a NaN wins, ties go to the lowest row.
+ * At most 256 partial results per column, added in index order by one lane: a result repeats bit for bit. */
+enum ssf_array_reduce_op { SSF_ARRAY_SUM = 0, SSF_ARRAY_SUMSQDEV = 1, SSF_ARRAY_MIN = 2, SSF_ARRAY_MAX = 3 };
+int  ssf_array_reduce(int device, int32_t op, int32_t dtype, int64_t rows, int32_t cols, const double *center, const void *x, double *out,
+                      int64_t *arg_out);
+/* freqShift (optic/dsp/core.py:1050-1072): out (n, ncols) complex128 = x exp(1j ((2 pi) deltaF) (k (1 / Fs))) with k the row, the
+ * phasor formed in the kernel.  x and out may be host or device memory. */
+int  ssf_freq_shift(int device, int64_t n, int32_t ncols, int32_t dtype, double deltaF, double Fs, const void *x, void *out);
+
 #ifdef __cplusplus
 }
 #endif

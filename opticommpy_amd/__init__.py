@@ -28,7 +28,7 @@ from .models import (  # noqa: F401
     last_run, set_device, set_engine,
 )
 
-from .device import DeviceArray, to_device  # noqa: F401
+from .device import DeviceArray, concatenate, freqShift, full, stack, to_device, zeros  # noqa: F401
 from .rx import (  # noqa: F401
     balancedPD, coherentReceiver, decimate, delaySignal, firFilter, iqMixing, lowPassFIR, opticalHybrid2x4, pbs,
     pdmCoherentReceiver, pdmCoherentReceiverChain, photodiode,
@@ -69,4 +69,5 @@ __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMa
            "gardnerTEDnyquist", "interpolator",
            "pamTransmitter", "mzm", "pm", "iqm", "voa", "upsample", "awgn", "bitSource", "prbsGenerator", "symbolSource",
            "mlse", "detector", "autocorr", "levinson", "estimateWhiteningFilter",
-           "syncDataSequences", "movingAverage", "bert", "theoryBER", "Qfunc"]
+           "syncDataSequences", "movingAverage", "bert", "theoryBER", "Qfunc",
+           "concatenate", "stack", "zeros", "full", "freqShift"]

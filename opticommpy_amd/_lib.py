@@ -225,6 +225,30 @@ CLOCK_FLUSH = 64           # outputs that leave in one store (kFlush)
 CLOCK_LAG = 128            # ... once the loop is this far ahead of the first of them (kLag)
 
 
+ARRAY_MAX_DIM = 4                                                                            # SSF_ARRAY_MAX_DIM
+
+
+class ArrayDesc(C.Structure):
+    """ssf_array_desc (include/ssf.h)."""
+    _fields_ = [("ndim", C.c_int32), ("itemsize", C.c_int32), ("offset", C.c_int64), ("extent", C.c_int64),
+                ("shape", C.c_int64 * ARRAY_MAX_DIM), ("stride", C.c_int64 * ARRAY_MAX_DIM)]
+
+
+class ArrayBinaryParams(C.Structure):
+    """ssf_array_binary_params (include/ssf.h)."""
+    _fields_ = [("op", C.c_int32), ("swap", C.c_int32), ("a_dtype", C.c_int32), ("b_dtype", C.c_int32), ("out_dtype", C.c_int32),
+                ("kind", C.c_int32), ("count", C.c_int64), ("inner", C.c_int64), ("scalar_re", C.c_double), ("scalar_im", C.c_double)]
+
+
+ARRAY_BINARY = {"add": 0, "sub": 1, "mul": 2, "div": 3}                                      # ssf_array_binary_op
+ARRAY_UNARY = {"neg": 0, "conj": 1, "real": 2, "imag": 3, "abs": 4, "abs2": 5, "angle": 6, "exp": 7, "sqrt": 8, "convert": 9}
+ARRAY_SAME, ARRAY_SCALAR, ARRAY_ROW, ARRAY_COLUMN = 0, 1, 2, 3                               # ssf_array_bcast
+ARRAY_SUM, ARRAY_SUMSQDEV, ARRAY_MIN, ARRAY_MAX = 0, 1, 2, 3                                 # ssf_array_reduce_op
+ARRAY_BLOCK = 256          # lanes per workgroup of the array engine's kernels (array_kernels.h: kBlock)
+ARRAY_MAX_BLOCKS = 4096    # workgroups of a grid-stride element-wise or movement pass (kMaxBlocks)
+ARRAY_RED_BLOCKS = 256     # partial results per column of a reduction (kRedBlocks)
+ARRAY_TILE = 32            # the transpose's LDS tile (kTile)
+
 EQ_ALGS = {"nlms": 0, "cma": 1, "rde": 2, "da-rde": 3, "dd-lms": 4, "static": 5}             # ssf_eq_alg
 EQ_CHUNK = 64              # output symbols the serial equalizer kernel stages per chunk (eq_kernels.h: kChunk)
 EQ_STAGE_ELEMS = 1024      # ... unless ((c - 1) SpS + nTaps) nModes input values would exceed its staging buffer (kStageElems)
@@ -424,6 +448,15 @@ SYMBOLS = {
     "ssf_clock_scale_add": (C.c_int, [C.c_int, C.c_int64, C.c_double, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ssf_gardner": (C.c_int, [C.c_int, C.POINTER(GardnerParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     "ssf_clock_drift": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
+    "ssf_array_copy": (C.c_int, [C.c_int, C.POINTER(ArrayDesc), C.c_void_p, C.POINTER(ArrayDesc), C.c_void_p]),
+    "ssf_array_take": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_array_transpose": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ssf_array_fill": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ssf_array_binary": (C.c_int, [C.c_int, C.POINTER(ArrayBinaryParams), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ssf_array_unary": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ssf_array_reduce": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_int64)]),
+    "ssf_freq_shift": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     "ssf_device_copy_bandwidth": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.POINTER(C.c_double)]),
     "ssf_linear_channel": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                      C.c_void_p, C.c_void_p]),

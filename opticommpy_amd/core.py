@@ -1,5 +1,6 @@
 """The signal-processing helpers under the reference's module name (optic/dsp/core.py), gathered from the modules that implement
 them."""
+from .device import freqShift  # noqa: F401
 from .clock import clockSamplingInterp, quantizer, resample  # noqa: F401
 from .imddtx import upsample  # noqa: F401
 from .metrics import anorm, pnorm, signalPower  # noqa: F401

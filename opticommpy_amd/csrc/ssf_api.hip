@@ -2,6 +2,7 @@
 #include <map>
 #include <memory>
 #include <thread>
+#include <utility>
 
 #include "ssf_internal.h"
 
@@ -1398,6 +1399,167 @@ int ssf_clock_drift(int device, int64_t n, int32_t ncols, int32_t per_column, co
     std::string err;
     int rc = ssf::clock_drift(device, n, ncols, per_column, t, ppm_out, &err);
     return rc ? set_err(rc, "ssf_clock_drift: " + err) : SSF_OK;
+}
+
+// ---- the array layer of DeviceArray (engine_array.hip): every check comes before the first allocation or launch
+static bool array_bad_dtype(int32_t d) { return d < SSF_M_C128 || d > SSF_M_F32; }
+static bool array_bad_itemsize(int32_t s) { return s != 1 && s != 2 && s != 4 && s != 8 && s != 16; }
+static const int64_t kArrayMax = (int64_t)1 << 40;            // elements of one array
+// every element the descriptor reaches lies in [0, extent)
+static bool array_bad_desc(const ssf_array_desc *d) {
+    if (d->ndim < 0 || d->ndim > SSF_ARRAY_MAX_DIM || array_bad_itemsize(d->itemsize) || d->extent < 0 || d->extent > kArrayMax) return true;
+    int64_t lo = d->offset, hi = d->offset, count = 1;
+    for (int a = 0; a < d->ndim; ++a) {
+        if (d->shape[a] < 0 || d->shape[a] > kArrayMax || d->stride[a] > kArrayMax || d->stride[a] < -kArrayMax) return true;
+        count *= d->shape[a];
+        if (count > kArrayMax) return true;
+    }
+    if (count == 0) return false;
+    if (d->offset < 0 || d->offset >= d->extent) return true;
+    for (int a = 0; a < d->ndim; ++a) {
+        if (d->shape[a] == 1) continue;
+        // an axis of more than one element steps by less than the allocation: its span (shape - 1) |stride| then fits 2^80 only
+        // in 128 bits, where it is formed; lo and hi stay within 4 x 2^80
+        const int64_t step = d->stride[a] < 0 ? -d->stride[a] : d->stride[a];
+        if (step >= d->extent) return true;
+        const __int128 span = (__int128)(d->shape[a] - 1) * step;
+        if (span >= d->extent) return true;
+        if (d->stride[a] < 0) lo -= (int64_t)span;
+        else hi += (int64_t)span;
+    }
+    return lo < 0 || hi >= d->extent;
+}
+// a destination must not write an element twice: with the axes of more than one element ordered by |stride|, each steps over
+// everything the ones before it reach
+static bool array_desc_overlaps(const ssf_array_desc *d) {
+    int64_t step[SSF_ARRAY_MAX_DIM], n[SSF_ARRAY_MAX_DIM];
+    int k = 0;
+    for (int a = 0; a < d->ndim; ++a) {
+        if (d->shape[a] == 0) return false;
+        if (d->shape[a] == 1) continue;
+        step[k] = d->stride[a] < 0 ? -d->stride[a] : d->stride[a], n[k] = d->shape[a], ++k;
+    }
+    for (int i = 1; i < k; ++i)
+        for (int j = i; j > 0 && step[j] < step[j - 1]; --j) std::swap(step[j], step[j - 1]), std::swap(n[j], n[j - 1]);
+    int64_t reach = 0;                       // the furthest element the axes so far reach (array_bad_desc: below extent)
+    for (int i = 0; i < k; ++i) {
+        if (step[i] <= reach) return true;
+        reach += (n[i] - 1) * step[i];
+    }
+    return false;
+}
+
+int ssf_array_copy(int device, const ssf_array_desc *src_desc, const void *src, const ssf_array_desc *dst_desc, void *dst) {
+    if (!src_desc || !dst_desc || !src || !dst) return set_err(SSF_ERR_BAD_ARG, "ssf_array_copy: NULL argument");
+    if (array_bad_desc(src_desc) || array_bad_desc(dst_desc)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_copy: a descriptor is malformed or leaves its array");
+    if (array_desc_overlaps(dst_desc)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_copy: the destination descriptor reaches an element twice");
+    if (src_desc->ndim != dst_desc->ndim || src_desc->itemsize != dst_desc->itemsize) return set_err(SSF_ERR_BAD_ARG, "ssf_array_copy: the two sides differ in ndim or itemsize");
+    int64_t count = 1;
+    for (int a = 0; a < src_desc->ndim; ++a) {
+        if (src_desc->shape[a] != dst_desc->shape[a]) return set_err(SSF_ERR_BAD_ARG, "ssf_array_copy: the two sides differ in shape");
+        count *= src_desc->shape[a];
+    }
+    if (src == dst) return set_err(SSF_ERR_BAD_ARG, "ssf_array_copy: in place is not supported");
+    if (count == 0) return SSF_OK;
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::array_copy(device, src_desc, src, dst_desc, dst, &err);
+    return rc ? set_err(rc, "ssf_array_copy: " + err) : SSF_OK;
+}
+
+int ssf_array_take(int device, int64_t n_src, int64_t n_idx, int64_t inner, int32_t itemsize, int32_t idx_itemsize, const void *idx,
+                   const void *src, void *dst) {
+    if (!idx || !src || !dst || src == dst) return set_err(SSF_ERR_BAD_ARG, "ssf_array_take: NULL argument or in place");
+    if (n_src < 1 || n_idx < 0 || inner < 0 || n_src > kArrayMax || n_idx > kArrayMax || inner > kArrayMax || (inner && (n_idx > kArrayMax / inner || n_src > kArrayMax / inner)))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_array_take: bad sizes");
+    if (array_bad_itemsize(itemsize) || (idx_itemsize != 4 && idx_itemsize != 8)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_take: bad itemsize");
+    if (n_idx == 0 || inner == 0) return SSF_OK;
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::array_take(device, n_src, n_idx, inner, itemsize, idx_itemsize, idx, src, dst, &err);
+    return rc ? set_err(rc, "ssf_array_take: " + err) : SSF_OK;
+}
+
+int ssf_array_transpose(int device, int64_t rows, int64_t cols, int32_t itemsize, const void *src, void *dst) {
+    if (!src || !dst || src == dst) return set_err(SSF_ERR_BAD_ARG, "ssf_array_transpose: NULL argument or in place");
+    if (rows < 0 || cols < 0 || rows > kArrayMax || cols > kArrayMax || (cols && rows > kArrayMax / cols) || array_bad_itemsize(itemsize))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_array_transpose: bad sizes");
+    if (((rows + 31) / 32) * ((cols + 31) / 32) > 0x7fffffffLL) return set_err(SSF_ERR_UNSUPPORTED, "ssf_array_transpose: too many tiles");
+    if (rows == 0 || cols == 0) return SSF_OK;
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::array_transpose(device, rows, cols, itemsize, src, dst, &err);
+    return rc ? set_err(rc, "ssf_array_transpose: " + err) : SSF_OK;
+}
+
+int ssf_array_fill(int device, int64_t count, int32_t itemsize, const void *value, void *dst) {
+    if (!value || !dst || count < 0 || count > kArrayMax || array_bad_itemsize(itemsize)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_fill: bad argument");
+    if (count == 0) return SSF_OK;
+    if (int rc = rx_check_device(device)) return rc;
+    if (ssf::on_device(value)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_fill: the value is host memory");
+    std::string err;
+    int rc = ssf::array_fill(device, count, itemsize, value, dst, &err);
+    return rc ? set_err(rc, "ssf_array_fill: " + err) : SSF_OK;
+}
+
+int ssf_array_binary(int device, const ssf_array_binary_params *p, const void *a, const void *b, void *out) {
+    if (!p || !a || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: NULL argument");
+    if (p->op < SSF_ARRAY_ADD || p->op > SSF_ARRAY_DIV || p->kind < SSF_ARRAY_SAME || p->kind > SSF_ARRAY_COLUMN || (p->swap != 0 && p->swap != 1))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: unknown op, kind or swap");
+    if (array_bad_dtype(p->a_dtype) || array_bad_dtype(p->b_dtype) || array_bad_dtype(p->out_dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: bad dtype");
+    if ((p->a_dtype <= SSF_M_C64 || p->b_dtype <= SSF_M_C64) != (p->out_dtype <= SSF_M_C64))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: the result is complex exactly if an operand is");
+    if (p->count < 0 || p->count > kArrayMax) return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: bad count");
+    if (p->kind != SSF_ARRAY_SCALAR && !b) return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: the second operand is NULL");
+    if ((p->kind == SSF_ARRAY_ROW || p->kind == SSF_ARRAY_COLUMN) && (p->inner < 1 || p->count % p->inner))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: inner must divide count");
+    if (a == out || b == out) return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: in place is not supported");
+    if (p->count == 0) return SSF_OK;
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::array_binary(device, p, a, b, out, &err);
+    return rc ? set_err(rc, "ssf_array_binary: " + err) : SSF_OK;
+}
+
+int ssf_array_unary(int device, int32_t op, int32_t in_dtype, int32_t out_dtype, int64_t count, const void *x, void *out) {
+    if (!x || !out || x == out) return set_err(SSF_ERR_BAD_ARG, "ssf_array_unary: NULL argument or in place");
+    if (op < SSF_ARRAY_NEG || op > SSF_ARRAY_CONVERT || array_bad_dtype(in_dtype) || array_bad_dtype(out_dtype) || count < 0 || count > kArrayMax)
+        return set_err(SSF_ERR_BAD_ARG, "ssf_array_unary: bad op, dtype or count");
+    const bool in_c = in_dtype <= SSF_M_C64, out_c = out_dtype <= SSF_M_C64;
+    const bool real_result = op >= SSF_ARRAY_REAL && op <= SSF_ARRAY_ANGLE;
+    if (op == SSF_ARRAY_SQRT && in_c) return set_err(SSF_ERR_UNSUPPORTED, "ssf_array_unary: sqrt of real arrays only");
+    if (real_result ? out_c : (op == SSF_ARRAY_CONVERT ? (in_c && !out_c) : in_c != out_c))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_array_unary: the result dtype does not fit the operation");
+    if (count == 0) return SSF_OK;
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::array_unary(device, op, in_dtype, out_dtype, count, x, out, &err);
+    return rc ? set_err(rc, "ssf_array_unary: " + err) : SSF_OK;
+}
+
+int ssf_array_reduce(int device, int32_t op, int32_t dtype, int64_t rows, int32_t cols, const double *center, const void *x, double *out,
+                     int64_t *arg_out) {
+    if (!x || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_array_reduce: NULL argument");
+    if (op < SSF_ARRAY_SUM || op > SSF_ARRAY_MAX || array_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_reduce: bad op or dtype");
+    if (rows < 1 || cols < 1 || cols > 65535 || rows > kArrayMax / cols) return set_err(SSF_ERR_BAD_ARG, "ssf_array_reduce: bad sizes");
+    if (op == SSF_ARRAY_SUMSQDEV && !center) return set_err(SSF_ERR_BAD_ARG, "ssf_array_reduce: the squared deviations need a centre");
+    if ((op == SSF_ARRAY_MIN || op == SSF_ARRAY_MAX) && (!arg_out || dtype <= SSF_M_C64))
+        return set_err(SSF_ERR_BAD_ARG, "ssf_array_reduce: min and max are for real arrays and need arg_out");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::array_reduce(device, op, dtype, rows, cols, op == SSF_ARRAY_SUMSQDEV ? center : nullptr, x, out, arg_out, &err);
+    return rc ? set_err(rc, "ssf_array_reduce: " + err) : SSF_OK;
+}
+
+int ssf_freq_shift(int device, int64_t n, int32_t ncols, int32_t dtype, double deltaF, double Fs, const void *x, void *out) {
+    if (!x || !out || x == out) return set_err(SSF_ERR_BAD_ARG, "ssf_freq_shift: NULL argument or in place");
+    if (n < 0 || ncols < 1 || n > kArrayMax / ncols || array_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_freq_shift: bad sizes or dtype");
+    if (!std::isfinite(deltaF) || !std::isfinite(Fs) || Fs == 0) return set_err(SSF_ERR_BAD_ARG, "ssf_freq_shift: deltaF must be finite, Fs finite and non-zero");
+    if (n == 0) return SSF_OK;
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::array_freq_shift(device, n, ncols, dtype, deltaF, Fs, x, out, &err);
+    return rc ? set_err(rc, "ssf_freq_shift: " + err) : SSF_OK;
 }
 
 }  // extern "C"

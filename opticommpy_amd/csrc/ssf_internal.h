@@ -247,6 +247,18 @@ int clock_gardner(int device, const ssf_gardner_params *p, const void *x, void *
                   std::string *err);
 int clock_drift(int device, int64_t n, int ncols, int per_column, const double *t, double *ppm_out, std::string *err);
 
+// engine_array.hip (arguments already checked by ssf_api.hip)
+int array_copy(int device, const ssf_array_desc *sdesc, const void *src, const ssf_array_desc *ddesc, void *dst, std::string *err);
+int array_take(int device, int64_t n_src, int64_t n_idx, int64_t inner, int itemsize, int idx_itemsize, const void *idx, const void *src,
+               void *dst, std::string *err);
+int array_transpose(int device, int64_t rows, int64_t cols, int itemsize, const void *src, void *dst, std::string *err);
+int array_fill(int device, int64_t count, int itemsize, const void *value, void *dst, std::string *err);
+int array_binary(int device, const ssf_array_binary_params *p, const void *a, const void *b, void *out, std::string *err);
+int array_unary(int device, int op, int in_dtype, int out_dtype, int64_t count, const void *x, void *out, std::string *err);
+int array_reduce(int device, int op, int dtype, int64_t rows, int cols, const double *center, const void *x, double *out, int64_t *arg_out,
+                 std::string *err);
+int array_freq_shift(int device, int64_t n, int ncols, int dtype, double deltaF, double Fs, const void *x, void *out, std::string *err);
+
 inline int fail(ssf_plan *p, int code, const std::string &msg) {
     if (p) p->err = msg;
     return code;

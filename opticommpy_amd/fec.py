@@ -28,7 +28,8 @@ Scope and limits (anything else raises ``ValueError`` before the library is load
 Deviations from the reference, on purpose:
 
 * ``transposed=True`` takes and returns ``(numCodewords, n_)`` arrays (what ``calcLLR(...).reshape(Nwords, -1)`` gives: a
-  ``DeviceArray`` has no ``.T``);
+  ``DeviceArray`` has no ``.T``).  It has one now (``opticommpy_amd/device.py``: a transposed copy), so the reference's own line
+  ``.reshape(Nwords, -1).T`` runs on the device too; ``transposed=True`` stays and saves that copy;
 * ``returnIter=True`` also returns ``lastIter`` (uint32), which the reference computes and only logs;
 * ``frameErrors`` and ``lastIter`` are numpy arrays whatever the input is (``numCodewords`` values);
 * an unsupported ``alg`` or a missing ``H`` raises (the reference logs an error and fails later);
