@@ -574,6 +574,22 @@ int  ssf_signal_power(int device, int64_t count, int64_t rows, int32_t dtype, co
 int  ssf_demodulate(int device, int64_t count, int32_t dtype, int32_t M, const double *const_raw, const void *symb,
                     int32_t *bits_out);
 
+/* ---- mutual information of a constellation on the circular AWGN channel (optic/comm/metrics.py:770-848 theoryMI, 497-547 calcMI).
+ * ssf_theory_mi: by quadrature, for nS noise deviations in one call.
+ *   const_tab   M (re, im) pairs, used as given;  px  M probabilities, finite and > 0;  sigma  nS deviations per dimension, > 0
+ *   mi_out      nS values, host:  H(X) - sum_i px_i E[ log2( sum_j px_j e^{e_ij} ) - log2 px_i ],
+ *               e_ij(t) = -(|d_ij|^2 + 2 sqrt(2) sigma Re(conj(d_ij) t)) / (2 sigma^2),  d_ij = x_i - x_j
+ * The expectation over t (density e^{-|t|^2} / pi) is a uniform grid: spacing h = 0.1, |Re t|, |Im t| <= 6.5 (131 x 131 nodes),
+ * weight e^{-|t|^2} h^2 / pi, not renormalised; the -log2 px_i term is multiplied by the grid's own weight sum, so a one-point table
+ * gives exactly 0.  The rule is within 1e-10 of the integral (profiles/theory_quadrature.json).  Sums run in a fixed order: results
+ * repeat bit for bit, and a value does not depend on which other deviations are asked for with it.  1 <= M <= 1024, 1 <= nS <= 4096.
+ * ssf_calc_mi: the Monte-Carlo estimate over n symbol pairs, the reference's direct form in double.
+ *   rx, tx      n values of `dtype` (ssf_metrics_dtype), host or device; never written
+ *   mi_out      one value, host */
+int  ssf_theory_mi(int device, int32_t M, int32_t nS, const double *const_tab, const double *px, const double *sigma, double *mi_out);
+int  ssf_calc_mi(int device, int64_t n, int32_t dtype, int32_t M, double sigma2, const double *const_tab, const double *px,
+                 const void *rx, const void *tx, double *mi_out);
+
 /* ---- carrier phase recovery on the device: blind phase search with an optional 4th-power frequency offset estimation ahead of
  * it (optic/dsp/carrierRecovery.py:37-169 cpr, 172-223 bps, 333-371 fourthPowerFOE; optic/dsp/carrierRecoveryGPU.py bpsGPU).
  *   x           (n, nModes) row-major, complex128 (SSF_M_C128) or complex64 (SSF_M_C64), host or device; never written

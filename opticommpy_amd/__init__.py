@@ -37,6 +37,10 @@ from .rx import (  # noqa: F401
 from .wdm_tx import basicLaserModel, grayMapping, phaseNoise, pulseShape, simpleWDMTx  # noqa: F401
 from . import metrics  # noqa: F401  (a callable module: oa.metrics(rx, tx, M, constType) returns all seven link metrics)
 from .metrics import calcEVM, demodulateGray, fastBERcalc, monteCarloGMI, monteCarloMI, anorm, pnorm, signalPower  # noqa: F401
+from . import theory  # noqa: F401
+from .theory import (  # noqa: F401
+    ASE_NyquistWDM, GN_Model_NyquistWDM, GNmodel_OSNR, calcLinOSNR, calcMI, condEntropy, constellationMI, theoryMI,
+)
 from . import cpr  # noqa: F401  (a callable module: oa.cpr(sigIn, param) is the reference's cpr)
 from .cpr import bps, bpsGPU, fourthPowerFOE  # noqa: F401
 from .sync import finddelay, symbolSync  # noqa: F401
@@ -70,4 +74,5 @@ __all__ = ["simpleWDMTx", "basicLaserModel", "pulseShape", "phaseNoise", "grayMa
            "pamTransmitter", "mzm", "pm", "iqm", "voa", "upsample", "awgn", "bitSource", "prbsGenerator", "symbolSource",
            "mlse", "detector", "autocorr", "levinson", "estimateWhiteningFilter",
            "syncDataSequences", "movingAverage", "bert", "theoryBER", "Qfunc",
+           "theoryMI", "constellationMI", "calcMI", "condEntropy", "GN_Model_NyquistWDM", "ASE_NyquistWDM", "GNmodel_OSNR", "calcLinOSNR",
            "concatenate", "stack", "zeros", "full", "freqShift"]

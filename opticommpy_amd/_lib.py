@@ -399,6 +399,10 @@ SYMBOLS = {
     "ssf_pnorm": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]),
     "ssf_signal_power": (C.c_int, [C.c_int, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_double)]),
     "ssf_demodulate": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]),
+    "ssf_theory_mi": (C.c_int, [C.c_int, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                C.POINTER(C.c_double)]),
+    "ssf_calc_mi": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                              C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]),
     "ssf_cpr": (C.c_int, [C.c_int, C.POINTER(CprParams), C.POINTER(C.c_double), C.c_void_p, C.c_void_p, C.c_void_p,
                           C.POINTER(C.c_double)]),
     "ssf_bps": (C.c_int, [C.c_int, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_void_p,

@@ -786,6 +786,46 @@ int ssf_demodulate(int device, int64_t count, int32_t dtype, int32_t M, const do
     return rc ? set_err(rc, "ssf_demodulate: " + err) : SSF_OK;
 }
 
+// ---- theoretical and Monte-Carlo mutual information (engine_theory.hip): every check comes before the first allocation or launch
+static bool theory_bad_px(const double *px, int32_t M) {
+    for (int m = 0; m < M; ++m)
+        if (!(px[m] > 0) || !std::isfinite(px[m])) return true;
+    return false;
+}
+static bool theory_bad_table(const double *tab, int32_t M) {
+    for (int m = 0; m < 2 * M; ++m)
+        if (!std::isfinite(tab[m])) return true;
+    return false;
+}
+
+int ssf_theory_mi(int device, int32_t M, int32_t nS, const double *const_tab, const double *px, const double *sigma, double *mi_out) {
+    if (!const_tab || !px || !sigma || !mi_out) return set_err(SSF_ERR_BAD_ARG, "ssf_theory_mi: NULL argument");
+    if (M < 1 || M > 1024) return set_err(SSF_ERR_BAD_ARG, "ssf_theory_mi: M must be 1 .. 1024");
+    if (nS < 1 || nS > 4096) return set_err(SSF_ERR_BAD_ARG, "ssf_theory_mi: nS must be 1 .. 4096");
+    if (theory_bad_table(const_tab, M)) return set_err(SSF_ERR_BAD_ARG, "ssf_theory_mi: the table must be finite");
+    if (theory_bad_px(px, M)) return set_err(SSF_ERR_BAD_ARG, "ssf_theory_mi: px must be finite and positive");
+    for (int s = 0; s < nS; ++s)
+        if (!(sigma[s] > 0) || !std::isfinite(sigma[s])) return set_err(SSF_ERR_BAD_ARG, "ssf_theory_mi: sigma must be finite and positive");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::theory_mi(device, M, nS, const_tab, px, sigma, mi_out, &err);
+    return rc ? set_err(rc, "ssf_theory_mi: " + err) : SSF_OK;
+}
+
+int ssf_calc_mi(int device, int64_t n, int32_t dtype, int32_t M, double sigma2, const double *const_tab, const double *px, const void *rx,
+                const void *tx, double *mi_out) {
+    if (!const_tab || !px || !rx || !tx || !mi_out) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_mi: NULL argument");
+    if (n < 1 || metrics_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_mi: bad n or dtype");
+    if (M < 1 || M > 1024) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_mi: M must be 1 .. 1024");
+    if (!(sigma2 > 0) || !std::isfinite(sigma2)) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_mi: sigma2 must be finite and positive");
+    if (theory_bad_table(const_tab, M)) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_mi: the table must be finite");
+    if (theory_bad_px(px, M)) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_mi: px must be finite and positive");
+    if (int rc = rx_check_device(device)) return rc;
+    std::string err;
+    int rc = ssf::theory_calc_mi(device, n, dtype, M, sigma2, const_tab, px, rx, tx, mi_out, &err);
+    return rc ? set_err(rc, "ssf_calc_mi: " + err) : SSF_OK;
+}
+
 // ---- carrier phase recovery (engine_cpr.hip): every check comes before the first allocation or launch
 static const char *cpr_bad_shape(int64_t n, int32_t nModes, int32_t dtype) {
     if (n < 2) return "n must be at least 2";

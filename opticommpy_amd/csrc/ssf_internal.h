@@ -174,6 +174,10 @@ int metrics_pnorm(int device, int64_t count, int dtype, const void *x, void *y, 
 int metrics_power(int device, int64_t count, int64_t rows, int dtype, const void *x, double *out, std::string *err);
 int metrics_demod(int device, int64_t count, int dtype, int M, const double *const_raw, const void *symb, int32_t *bits_out,
                   std::string *err);
+// engine_theory.hip (arguments already checked by ssf_api.hip)
+int theory_mi(int device, int M, int nS, const double *const_tab, const double *px, const double *sigma, double *mi_out, std::string *err);
+int theory_calc_mi(int device, int64_t n, int dtype, int M, double sigma2, const double *const_tab, const double *px, const void *rx,
+                   const void *tx, double *mi_out, std::string *err);
 // engine_cpr.hip (arguments already checked by ssf_api.hip)
 int cpr_run(int device, const ssf_cpr_params *p, const double *table, const void *x, void *sig_out, double *phase_out, double *fo_out,
             std::string *err);

@@ -29,10 +29,14 @@ import numpy as np
 from . import _lib
 from . import device as _dev
 from .synchronization import Qfunc, bert, theoryBER  # noqa: F401  (optic/comm/metrics.py names them; they live with syncDataSequences)
+from .theory import (  # noqa: F401  (optic/comm/metrics.py names them; they live in theory.py)
+    ASE_NyquistWDM, GN_Model_NyquistWDM, GNmodel_OSNR, calcLinOSNR, calcMI, condEntropy, constellationMI, theoryMI,
+)
 from .wdm_tx import grayMapping
 
 __all__ = ["fastBERcalc", "monteCarloGMI", "monteCarloMI", "calcEVM", "demodulateGray", "pnorm", "anorm", "signalPower", "metrics",
-           "bert", "theoryBER", "Qfunc"]
+           "bert", "theoryBER", "Qfunc", "theoryMI", "constellationMI", "calcMI", "condEntropy", "GN_Model_NyquistWDM", "ASE_NyquistWDM",
+           "GNmodel_OSNR", "calcLinOSNR"]
 
 _NAMES = ("BER", "SER", "SNR", "GMI", "NGMI", "MI", "EVM")
 
