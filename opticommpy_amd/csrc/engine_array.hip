@@ -315,10 +315,7 @@ template <typename T> struct RunFill {
 
 bool all_device(Call &c, std::initializer_list<const void *> ps) {
     for (const void *p : ps)
-        if (!on_device(p)) {
-            c.rc = SSF_ERR_BAD_ARG, *c.err = "array data must be device memory";
-            return false;
-        }
+        if (!on_device(p)) return c.reject(SSF_ERR_BAD_ARG, "array data must be device memory");
     return true;
 }
 
@@ -420,7 +417,7 @@ int array_reduce(int device, int op, int dtype, int64_t rows, int cols, const do
         if (!c.launched()) return c.rc;
         k_reduce_sum_fold<<<fold_blocks, 64, 0, w.st>>>(nb, cols, (const double *)w.part.p, (double *)w.res.p);
         if (!c.launched()) return c.rc;
-        if (!c.ok(hipMemcpyAsync(out, w.res.p, (size_t)cols * 2 * sizeof(double), hipMemcpyDeviceToHost, w.st), "hipMemcpy") || !c.sync()) return c.rc;
+        if (!c.deliver(out, w.res.p, (size_t)cols * 2 * sizeof(double)) || !c.sync()) return c.rc;
         return SSF_OK;
     }
     if (!c.need(w.parg, (size_t)cols * nb * sizeof(long long)) || !c.need(w.rarg, (size_t)cols * sizeof(long long))) return c.rc;
@@ -429,9 +426,7 @@ int array_reduce(int device, int op, int dtype, int64_t rows, int cols, const do
     k_reduce_extreme_fold<<<fold_blocks, 64, 0, w.st>>>(op, nb, cols, (const double *)w.part.p, (const long long *)w.parg.p, (double *)w.res.p,
                                                          (long long *)w.rarg.p);
     if (!c.launched()) return c.rc;
-    if (!c.ok(hipMemcpyAsync(out, w.res.p, (size_t)cols * sizeof(double), hipMemcpyDeviceToHost, w.st), "hipMemcpy") ||
-        !c.ok(hipMemcpyAsync(arg_out, w.rarg.p, (size_t)cols * sizeof(long long), hipMemcpyDeviceToHost, w.st), "hipMemcpy") || !c.sync())
-        return c.rc;
+    if (!c.deliver(out, w.res.p, (size_t)cols * sizeof(double)) || !c.deliver(arg_out, w.rarg.p, (size_t)cols * sizeof(long long)) || !c.sync()) return c.rc;
     return SSF_OK;
 }
 

@@ -321,7 +321,7 @@ int clock_minmax(int device, int64_t count, int dtype, const void *x, double *ou
     if (!c.launched()) return c.rc;
     k_clock_minmax_fold<<<1, kBlock, 0, w.st>>>((int)nb, (const double *)w.part.p, (double *)w.res.p);
     if (!c.launched()) return c.rc;
-    if (!c.ok(hipMemcpyAsync(out2, w.res.p, 2 * sizeof(double), hipMemcpyDeviceToHost, w.st), "hipMemcpy") || !c.sync()) return c.rc;
+    if (!c.deliver(out2, w.res.p, 2 * sizeof(double)) || !c.sync()) return c.rc;
     return SSF_OK;
 }
 
@@ -365,8 +365,7 @@ int clock_gardner(int device, const ssf_gardner_params *p, const void *x, void *
     if (!c.launched()) return c.rc;
     std::vector<int> status(nModes);
     std::vector<long long> last(nModes);
-    if (!c.ok(hipMemcpyAsync(last.data(), w.last.p, (size_t)nModes * sizeof(long long), hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return c.rc;
-    if (!c.ok(hipMemcpyAsync(status.data(), w.status.p, (size_t)nModes * sizeof(int), hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return c.rc;
+    if (!c.deliver(last.data(), w.last.p, (size_t)nModes * sizeof(long long)) || !c.deliver(status.data(), w.status.p, (size_t)nModes * sizeof(int))) return c.rc;
     if (!c.deliver(sig_out, sig, sig_bytes) || !c.deliver(t_out, tv, t_bytes) || !c.sync()) return c.rc;
     for (int k = 0; k < nModes; ++k) {
         last_n[k] = last[k];
@@ -390,8 +389,7 @@ int clock_drift(int device, int64_t n, int ncols, int per_column, const double *
     if (!c.launched()) return c.rc;
     k_drift_peaks<<<ncols, kBlock, 0, w.st>>>(n, ncols, per_column, td, (const double *)w.part.p, (double *)w.res.p);
     if (!c.launched()) return c.rc;
-    if (!c.ok(hipMemcpyAsync(ppm_out, w.res.p, (size_t)ncols * sizeof(double), hipMemcpyDeviceToHost, w.st), "hipMemcpy") || !c.sync())
-        return c.rc;
+    if (!c.deliver(ppm_out, w.res.p, (size_t)ncols * sizeof(double)) || !c.sync()) return c.rc;
     return SSF_OK;
 }
 

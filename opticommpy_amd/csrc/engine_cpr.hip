@@ -272,7 +272,7 @@ __global__ __launch_bounds__(kBlock) void k_foe_derotate(FoeArgs a) {
 struct Work : WorkBase {
     Buf tables, in, xw, f, phi, phase, loc, bsum, part, scal, cand_m, cand_i, peak, slope, out;
     FftPlans plans;
-    std::vector<double> host_tab, host_slope;     // sources of asynchronous uploads: they outlive the call
+    std::vector<double> host_tab, host_slope;     // kept for their capacity
 };
 using Call = CallT<Work>;
 
@@ -309,8 +309,7 @@ bool run_bps(Call &c, const void *x, int dtype, long long n, int nModes, int Nh,
         rot[2 * b] = std::cos(testph[b]), rot[2 * b + 1] = std::sin(testph[b]);
     }
     if (sep) host.insert(host.end(), lre.begin(), lre.end()), host.insert(host.end(), lim.begin(), lim.end());
-    if (!c.need(w.tables, host.size() * sizeof(double))) return false;
-    if (!c.ok(hipMemcpyAsync(w.tables.p, host.data(), host.size() * sizeof(double), hipMemcpyHostToDevice, w.st), "hipMemcpy")) return false;
+    if (!c.upload(w.tables, host)) return false;
     BpsArgs a{};
     a.x = x, a.dtype = dtype, a.nModes = nModes, a.Nh = Nh, a.B = B, a.M = M, a.n = n;
     a.W = kTile + 2 * Nh;
@@ -350,17 +349,13 @@ bool run_foe(Call &c, const void *x, int dtype, long long n, int nModes, int P, 
     std::vector<long long> peak(nModes);
     std::vector<double> &slope = w.host_slope;
     slope.assign(nModes, 0.0);
-    if (!c.ok(hipMemcpyAsync(peak.data(), w.peak.p, nModes * sizeof(long long), hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return false;
-    if (!c.sync()) return false;
+    if (!c.deliver(peak.data(), w.peak.p, nModes * sizeof(long long)) || !c.sync()) return false;
     for (int m = 0; m < nModes; ++m) {
-        if (peak[m] < 0 || peak[m] >= n) {
-            c.rc = SSF_ERR_BAD_ARG, *c.err = "no spectral maximum (the input is not finite)";
-            return false;
-        }
+        if (peak[m] < 0 || peak[m] >= n) return c.reject(SSF_ERR_BAD_ARG, "no spectral maximum (the input is not finite)");
         fo[m] = foe_frequency(peak[m], n, Fs, P);
         slope[m] = foe_slope(fo[m]);
     }
-    if (!c.ok(hipMemcpyAsync(w.slope.p, slope.data(), nModes * sizeof(double), hipMemcpyHostToDevice, w.st), "hipMemcpy")) return false;
+    if (!c.h2d(w.slope.p, slope.data(), nModes * sizeof(double))) return false;
     k_foe_derotate<<<nbf, kBlock, 0, w.st>>>(a);
     if (!c.launched()) return false;
     *nb_out = nbf;

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kBlock) void k_modulate(ModArgs a) {
 
 struct Work : WorkBase {
     Buf in, out, tab;
-    std::vector<double> host_tab;             // source of an asynchronous upload: it outlives the call
+    std::vector<double> host_tab;             // kept for its capacity
 };
 using Call = CallT<Work>;
 
@@ -193,16 +193,14 @@ int enc_modulate(int device, int64_t nsymb, int M, const double *table, const vo
     Work &w = *c.w;
     int b = 0;
     while ((1 << b) < M) ++b;
-    const size_t out_bytes = (size_t)nsymb * 2 * sizeof(double), tab_bytes = (size_t)M * 2 * sizeof(double);
+    const size_t out_bytes = (size_t)nsymb * 2 * sizeof(double);
     ModArgs a{};
     a.out = (double2 *)c.target(symb_out, w.out, out_bytes);
     if (!a.out) return c.rc;
     a.bits = (const unsigned char *)c.input(bits, w.in, (size_t)nsymb * b);
     if (!a.bits) return c.rc;
-    if (!c.sync()) return c.rc;               // an earlier call's upload may still read host_tab
     w.host_tab.assign(table, table + 2 * (size_t)M);
-    if (!c.need(w.tab, tab_bytes)) return c.rc;
-    if (!c.ok(hipMemcpyAsync(w.tab.p, w.host_tab.data(), tab_bytes, hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
+    if (!c.upload(w.tab, w.host_tab)) return c.rc;
     a.tab = (const double *)w.tab.p, a.n = nsymb, a.M = M, a.b = b;
     k_modulate<<<grid_blocks(nsymb, kBlock, 8192), kBlock, 0, w.st>>>(a);
     if (!c.launched()) return c.rc;

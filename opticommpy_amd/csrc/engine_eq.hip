@@ -239,7 +239,7 @@ __global__ __launch_bounds__(kStaticBlock) void k_eq_static(StaticArgs a) {
 // ---- host side
 struct Work : WorkBase {
     Buf in, refin, H, tables, out, esq;
-    std::vector<double> host_tab;             // sources of asynchronous uploads: they outlive the call
+    std::vector<double> host_tab;             // kept for their capacity
     std::vector<Seg> host_segs;
 };
 using Call = CallT<Work>;
@@ -265,7 +265,7 @@ int eq_run(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const
         rd = c.input(ref, w.refin, (size_t)p->nref * nModes * mk::elem_size(p->ref_dtype));
         if (!rd) return c.rc;
     }
-    if (H != H_inout && !c.ok(hipMemcpyAsync(H, H_inout, H_bytes, hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
+    if (H != H_inout && !c.h2d(H, H_inout, H_bytes)) return c.rc;
     // symbols no stage reaches stay zero, and so does |e|^2 of a static stage
     if (!c.ok(hipMemsetAsync(y, 0, out_bytes, w.st), "hipMemset")) return c.rc;
     if (esq && !c.ok(hipMemsetAsync(esq, 0, esq_bytes, w.st), "hipMemset")) return c.rc;
@@ -273,8 +273,7 @@ int eq_run(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, const
     std::vector<double> &tab = w.host_tab;
     tab.assign(table, table + 2 * (size_t)p->M);
     tab.insert(tab.end(), radii, radii + p->nRadii);
-    if (!c.need(w.tables, tab.size() * sizeof(double))) return c.rc;
-    if (!c.ok(hipMemcpyAsync(w.tables.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
+    if (!c.upload(w.tables, tab)) return c.rc;
 
     // runs of consecutive adaptive stages -> one serial launch each (per kMaxSegs stages); a static stage -> one parallel launch
     std::vector<Seg> &segs = w.host_segs;

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(kBlock) void k_finish(DecArgs a, int last, int *d_f
 // ---- host side
 struct Work : WorkBase {
     Buf in, tables, out, bits, fail, iter, msg, llr, post, hard, flags, state;
-    std::vector<unsigned char> host_tab;      // source of an asynchronous upload: it outlives the call
+    std::vector<unsigned char> host_tab;      // kept for their capacity
     std::vector<int> host_done;
 };
 using Call = CallT<Work>;
@@ -222,8 +222,7 @@ bool run_global(Call &c, const DecArgs &a, int sync_every, int *d_fail, uint32_t
         if (!c.launched()) return false;
         if (sync_every > 0 && it > 0 && it % sync_every == 0 && it + 1 < a.maxIter) {
             w.host_done.resize((size_t)a.ncw);
-            if (!c.ok(hipMemcpyAsync(w.host_done.data(), a.done, (size_t)a.ncw * sizeof(int), hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return false;
-            if (!c.sync()) return false;
+            if (!c.deliver(w.host_done.data(), a.done, (size_t)a.ncw * sizeof(int)) || !c.sync()) return false;
             bool all = true;
             for (int d : w.host_done) all = all && d;
             if (all) {
@@ -266,8 +265,7 @@ int fec_calc_llr(int device, int64_t n, int dtype, int M, double sigma2, const d
         }
         hz[i] = z, ho[i] = o;
     }
-    if (!c.need(w.tables, tab_bytes)) return c.rc;
-    if (!c.ok(hipMemcpyAsync(w.tables.p, w.host_tab.data(), tab_bytes, hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
+    if (!c.upload(w.tables, w.host_tab)) return c.rc;
     LlrArgs a{};
     a.x = xd, a.dtype = dtype, a.M = M, a.b = b, a.n = n, a.sigma2 = sigma2, a.out = out;
     a.tab = (const double *)w.tables.p, a.px = a.tab + 2 * (size_t)M;

@@ -1,8 +1,13 @@
-// engine_host.h -- the host half that the DSP engines share (engine_metrics, engine_cpr, engine_eq, engine_fec, engine_sync; HIP
-// only, nothing else includes it): grow-only device buffers, the per-engine state and the prologue of an entry point, staging of
-// array arguments and results, the launch grid, the rocFFT plan cache and the upload of numpy's pairwise leaves.
-// An engine brings its own `Work` (derived from WorkBase: its Bufs, and the host vectors its asynchronous uploads read) and
+// engine_host.h -- the host half that the DSP engines share.  Every engine_*.hip whose entry points start with a `Call` includes
+// it (HIP only, nothing else does): grow-only device buffers, the per-engine state and the prologue of an entry point, staging of
+// array arguments and results, uploads, the launch grid, the rocFFT plan cache and the upload of numpy's pairwise leaves.
+// An engine brings its own `Work` (derived from WorkBase: its Bufs, and host vectors kept between calls for their capacity) and
 // names `using Call = CallT<Work>`; every entry point then starts with `Call c(device, err); if (c.rc) return c.rc;`.
+//
+// The invariant: whenever an engine's lock is free, its stream is idle.  A call that succeeds ends with sync(); a call that fails
+// waits on the stream at the moment the failure is recorded.  Host memory that a call handed to the stream -- the caller's arrays,
+// the call's own locals, a vector in Work -- is therefore no longer referenced after any return, and the next call may overwrite
+// or free it without a wait of its own.  An entry point's part: return at the first failure, enqueue nothing after it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocfft/rocfft.h>
@@ -11,6 +16,7 @@
 #include <mutex>
 #include <string>
 #include <tuple>
+#include <utility>
 #include <vector>
 
 #include "metrics_kernels.h"
@@ -59,22 +65,20 @@ template <class W> struct CallT {
     }
     bool ok(hipError_t e, const char *what) {
         if (e == hipSuccess) return true;
-        rc = e == hipErrorOutOfMemory ? SSF_ERR_OOM : SSF_ERR_HIP;
-        *err = std::string(what) + ": " + hipGetErrorString(e);
-        (void)hipGetLastError();
-        return false;
+        return fail(e == hipErrorOutOfMemory ? SSF_ERR_OOM : SSF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
     }
-    bool fft_fail(const char *what) {
-        rc = SSF_ERR_FFT, *err = what;
-        return false;
-    }
+    bool fft_fail(const char *what) { return fail(SSF_ERR_FFT, what); }
+    // a failure the engine finds itself (a result it read back, an argument only it can judge)
+    bool reject(int code, const char *message) { return fail(code, message); }
     bool need(Buf &b, size_t bytes) { return ok(b.need(bytes), "hipMalloc"); }
+    // host memory to device memory on the call's stream; the host side only has to live until the call returns
+    bool h2d(void *dev, const void *host, size_t bytes) { return ok(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, w->st), "hipMemcpy"); }
+    bool upload(Buf &b, const void *host, size_t bytes) { return need(b, bytes) && h2d(b.p, host, bytes); }
+    template <class T> bool upload(Buf &b, const std::vector<T> &host) { return upload(b, host.data(), host.size() * sizeof(T)); }
     // device view of an array argument: a device pointer as it is, host memory through a staging buffer
     const void *input(const void *p, Buf &stage, size_t bytes) {
         if (on_device(p)) return p;
-        if (!need(stage, bytes)) return nullptr;
-        if (!ok(hipMemcpyAsync(stage.p, p, bytes, hipMemcpyHostToDevice, w->st), "hipMemcpy")) return nullptr;
-        return stage.p;
+        return upload(stage, p, bytes) ? stage.p : nullptr;
     }
     // where a result is computed: the caller's device memory, or `stage` when the caller's pointer is host memory (or NULL)
     void *target(void *user, Buf &stage, size_t bytes) {
@@ -87,6 +91,16 @@ template <class W> struct CallT {
     }
     bool launched() { return ok(hipGetLastError(), "kernel launch"); }
     bool sync() { return ok(hipStreamSynchronize(w->st), "hipStreamSynchronize"); }
+
+  private:
+    // the one way a call fails: the first failure keeps rc and *err, and the stream is drained before anyone can return (the
+    // header's invariant; a constructor that failed has no stream yet, a call with stream = false no Work)
+    bool fail(int code, std::string message) {
+        if (rc == SSF_OK) rc = code, *err = std::move(message);
+        if (w && w->st) (void)hipStreamSynchronize(w->st);
+        (void)hipGetLastError();
+        return false;
+    }
 };
 
 // workgroups of `block` lanes for a grid-stride loop over `count` elements.  The number of workgroups is the number of partial
@@ -137,19 +151,16 @@ template <class C> bool transform(C &c, void *buf, long long length, int batch, 
 // ---- the leaves of numpy's pairwise sum over n elements (mk::pw_leaves), on the device: nleaf + 1 starts, the last one n
 struct PwLeaves {
     Buf start;
-    std::vector<long long> host;              // source of an asynchronous upload: it outlives the call
+    std::vector<long long> host;              // kept for its capacity
     long long of = -1;                        // the n that `start` holds, kept while n stays the same
 };
 template <class C> bool pairwise_leaves(C &c, PwLeaves &l, long long n, long long &nleaf, const long long *&leaf_start) {
     nleaf = mk::pw_leaves(n, nullptr);
     if (l.of != n) {
-        if (!c.sync()) return false;                                // an earlier upload may still read l.host
         l.host.assign(nleaf + 1, n);
         mk::pw_leaves(n, l.host.data());
         l.of = -1;
-        if (!c.need(l.start, l.host.size() * sizeof(long long))) return false;
-        if (!c.ok(hipMemcpyAsync(l.start.p, l.host.data(), l.host.size() * sizeof(long long), hipMemcpyHostToDevice, c.w->st), "hipMemcpy"))
-            return false;
+        if (!c.upload(l.start, l.host)) return false;
         l.of = n;
     }
     leaf_start = (const long long *)l.start.p;

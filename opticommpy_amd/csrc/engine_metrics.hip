@@ -196,7 +196,7 @@ __global__ __launch_bounds__(kBlock) void k_scale(KArgs a, void *y) {
 struct Work : WorkBase {
     Buf tables, part, scal, res, idx, leaf_sum, in_rx, in_tx, out;
     PwLeaves leaves;
-    std::vector<double> host_tab;             // sources of asynchronous uploads: they outlive the call
+    std::vector<double> host_tab;             // kept for their capacity
     std::vector<float> host_w32;
 };
 using Call = CallT<Work>;
@@ -239,9 +239,7 @@ int metrics_run(int device, const ssf_metrics_params *p, const void *rx, const v
     const size_t in_bytes = (size_t)p->n * nModes * elem_size(p->dtype);
     if (!(a.rx = c.input(rx, w.in_rx, in_bytes))) return c.rc;
     if (tx && !(a.tx = c.input(tx, w.in_tx, in_bytes))) return c.rc;
-    if (!c.ok(hipMemcpyAsync(w.tables.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
-    if (!c.ok(hipMemcpyAsync((char *)w.tables.p + tab_bytes, w32.data(), M * sizeof(float), hipMemcpyHostToDevice, w.st), "hipMemcpy"))
-        return c.rc;
+    if (!c.h2d(w.tables.p, tab.data(), tab_bytes) || !c.h2d((char *)w.tables.p + tab_bytes, w32.data(), M * sizeof(float))) return c.rc;
     a.raw = (const double *)w.tables.p, a.cn = a.raw + 2 * M, a.px = a.raw + 4 * M, a.log2px = a.raw + 5 * M;
     a.w32 = (const float *)((char *)w.tables.p + tab_bytes);
     a.part = (double *)w.part.p, a.scal = (double *)w.scal.p, a.res = (double *)w.res.p;
@@ -332,11 +330,10 @@ int metrics_demod(int device, int64_t count, int dtype, int M, const double *con
     int bits = 0;
     while ((1 << bits) < M) ++bits;
     const size_t out_bytes = (size_t)count * bits * sizeof(int32_t);
-    if (!c.need(w.tables, 2 * (size_t)M * sizeof(double))) return c.rc;
+    if (!c.upload(w.tables, const_raw, 2 * (size_t)M * sizeof(double))) return c.rc;
     int32_t *od = (int32_t *)c.target(bits_out, w.out, out_bytes);
     if (!od) return c.rc;
     if (!(a.rx = c.input(symb, w.in_rx, (size_t)count * elem_size(dtype)))) return c.rc;
-    if (!c.ok(hipMemcpyAsync(w.tables.p, const_raw, 2 * (size_t)M * sizeof(double), hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
     a.n = count, a.M = M, a.bits = bits, a.dtype = dtype, a.raw = (const double *)w.tables.p;
     k_demod<<<grid_blocks(count, kBlock, kMaxBlocks), kBlock, 2 * M * sizeof(double), w.st>>>(a, od);
     if (!c.launched()) return c.rc;

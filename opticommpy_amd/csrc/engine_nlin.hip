@@ -68,7 +68,7 @@ struct PlanTables {
     uint64_t key = 0;
     Buf tab;                      // [pass | nidx | phase_m | pad to 16 | coef | phase_c]
     size_t sig[5] = {0, 0, 0, 0, 0};          // L, npass, ncoef, nphase, dense: what the entries were checked against
-    std::vector<char> host;       // source of the asynchronous upload: it outlives the call
+    std::vector<char> host;       // kept for its capacity
 };
 struct Work : WorkBase {
     Buf in0, in1, out[4], e1, xs, part, red, total;
@@ -101,7 +101,6 @@ const char *tables(Call &c, const ssf_nlin_params *p, const int32_t *pass, const
                 w.plans.splice(w.plans.begin(), w.plans, it);
                 return (const char *)it->tab.p;
             }
-    if (!c.sync()) return nullptr;            // an earlier upload may still read a plan's host copy
     if (w.plans.size() >= kPlans) w.plans.splice(w.plans.begin(), w.plans, std::prev(w.plans.end()));
     else w.plans.emplace_front();
     PlanTables &t = w.plans.front();
@@ -113,8 +112,7 @@ const char *tables(Call &c, const ssf_nlin_params *p, const int32_t *pass, const
     if (p->nphase) std::memcpy(t.host.data() + o.phase_m, phase_m, (size_t)p->nphase * sizeof(int32_t));
     if (p->ncoef) std::memcpy(t.host.data() + o.coef, coef, (size_t)p->ncoef * 16);
     if (p->nphase) std::memcpy(t.host.data() + o.phase_c, phase_c, (size_t)p->nphase * 16);
-    if (!c.need(t.tab, o.bytes)) return nullptr;
-    if (!c.ok(hipMemcpyAsync(t.tab.p, t.host.data(), o.bytes, hipMemcpyHostToDevice, w.st), "hipMemcpy")) return nullptr;
+    if (!c.upload(t.tab, t.host)) return nullptr;
     t.key = p->plan_key;
     std::memcpy(t.sig, sig, sizeof(sig));
     return (const char *)t.tab.p;

@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(kBlock) k_chan(const ChanArgs a) {
 struct Work : WorkBase {
     Buf in, out, work, Y, habs, hpha, mean, H, mod_tab, demod_tab;
     FftPlans plans;
-    std::vector<int> host_mod, host_demod;    // sources of asynchronous uploads: they outlive the call
+    std::vector<int> host_mod, host_demod;    // kept for their capacity
     uint64_t mod_key = 0, demod_key = 0;      // what mod_tab / demod_tab hold (0: nothing that can be named)
     long long mod_sig[3] = {0, 0, 0}, demod_sig[6] = {0, 0, 0, 0, 0, 0};
     std::set<const void *> armed;             // kernels whose dynamic-LDS limit has been raised on this device
@@ -103,11 +103,6 @@ template <class F> void dispatch(int lg, F &&f) {
     }
 }
 
-bool upload(Call &c, Buf &b, const std::vector<int> &host) {
-    return c.need(b, host.size() * sizeof(int)) &&
-           c.ok(hipMemcpyAsync(b.p, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice, c.w->st), "hipMemcpy");
-}
-
 }  // namespace
 
 int ofdm_modulate(int device, const ssf_ofdm_params *p, const int32_t *src_map, const void *symb, void *out, std::string *err) {
@@ -130,10 +125,9 @@ int ofdm_modulate(int device, const ssf_ofdm_params *p, const int32_t *src_map, 
     if (!a.symb) return c.rc;
     const long long sig[3] = {L, p->Ni, lds};
     if (!p->plan_key || p->plan_key != w.mod_key || sig[0] != w.mod_sig[0] || sig[1] != w.mod_sig[1] || sig[2] != w.mod_sig[2]) {
-        if (!c.sync()) return c.rc;           // an earlier upload may still read host_mod
         w.mod_key = 0;
         mod_table(src_map, (int)L, lg, w.host_mod);
-        if (!upload(c, w.mod_tab, w.host_mod)) return c.rc;
+        if (!c.upload(w.mod_tab, w.host_mod)) return c.rc;
         w.mod_key = p->plan_key, w.mod_sig[0] = sig[0], w.mod_sig[1] = sig[1], w.mod_sig[2] = sig[2];
     }
     a.map = (const int *)w.mod_tab.p;
@@ -184,10 +178,9 @@ int ofdm_demodulate(int device, const ssf_ofdm_params *p, const int32_t *bin_car
     bool same = p->plan_key && p->plan_key == w.demod_key;
     for (int i = 0; i < 6; ++i) same = same && dsig[i] == w.demod_sig[i];
     if (!same) {
-        if (!c.sync()) return c.rc;           // an earlier upload may still read host_demod
         w.demod_key = 0;
         demod_tables(bin_carrier, data_carriers, pilot_carriers, pilot_hi, Nfft, Ns, Ni, Np, lg, w.host_demod);
-        if (!upload(c, w.demod_tab, w.host_demod)) return c.rc;
+        if (!c.upload(w.demod_tab, w.host_demod)) return c.rc;
         w.demod_key = p->plan_key;
         for (int i = 0; i < 6; ++i) w.demod_sig[i] = dsig[i];
     }

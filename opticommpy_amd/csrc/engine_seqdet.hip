@@ -268,7 +268,7 @@ __global__ __launch_bounds__(64) void k_autocorr_fin(AcArgs a) {
 // ---- host side
 struct Work : WorkBase {
     Buf in, out, ind, tables, surv, maps, ends, fin, part, res;
-    std::vector<double> host_tab;             // source of an asynchronous upload: it outlives the call
+    std::vector<double> host_tab;             // kept for its capacity
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
 };
 using Call = CallT<Work>;
@@ -292,8 +292,7 @@ bool upload_tables(Call &c, const double *a, size_t na, const double *b, size_t 
     w.host_tab.assign(a, a + na);
     if (b) w.host_tab.insert(w.host_tab.end(), b, b + nb);
     else w.host_tab.insert(w.host_tab.end(), nb, 0.0);
-    const size_t bytes = w.host_tab.size() * sizeof(double);
-    return c.need(w.tables, bytes) && c.ok(hipMemcpyAsync(w.tables.p, w.host_tab.data(), bytes, hipMemcpyHostToDevice, w.st), "hipMemcpy");
+    return c.upload(w.tables, w.host_tab);
 }
 
 }  // namespace
@@ -346,8 +345,7 @@ int mlse_run(int device, ssf_mlse_params *p, const double *h, const double *cons
     k_mlse_walk<<<(unsigned)((nchunks * p->cols + 255) / 256), 256, 0, w.st>>>(b);
     if (!c.launched()) return c.rc;
     if (p->timing && !c.ok(hipEventRecord(w.ev[2], w.st), "hipEventRecord")) return c.rc;
-    if (!c.ok(hipMemcpyAsync(final_metric, f.fin_metric, (size_t)p->cols * sizeof(double), hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return c.rc;
-    if (!c.deliver(out, o, io_bytes) || !c.sync()) return c.rc;
+    if (!c.deliver(final_metric, f.fin_metric, (size_t)p->cols * sizeof(double)) || !c.deliver(out, o, io_bytes) || !c.sync()) return c.rc;
     p->fwd_ms = p->tb_ms = 0.0;
     if (p->timing) {
         float a = 0.f, d = 0.f;
@@ -392,7 +390,7 @@ int autocorr_run(int device, int64_t n, int nTaps, const void *x, double *r_out,
     k_autocorr<<<a.nb, kAcBlock, 0, w.st>>>(a);
     k_autocorr_fin<<<nTaps, 64, 0, w.st>>>(a);
     if (!c.launched()) return c.rc;
-    if (!c.ok(hipMemcpyAsync(r_out, a.r, (size_t)nTaps * sizeof(double), hipMemcpyDeviceToHost, w.st), "hipMemcpy") || !c.sync()) return c.rc;
+    if (!c.deliver(r_out, a.r, (size_t)nTaps * sizeof(double)) || !c.sync()) return c.rc;
     return SSF_OK;
 }
 

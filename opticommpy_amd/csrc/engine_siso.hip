@@ -354,7 +354,7 @@ __global__ __launch_bounds__(kTile) void k_siso_frozen(FrozenArgs a) {
 // ---- host side
 struct Work : WorkBase {
     Buf in, refin, coef, tables, out, mse, part, scal;
-    std::vector<double> host_tab;             // source of an asynchronous upload: it outlives the call
+    std::vector<double> host_tab;             // kept for its capacity
 };
 using Call = CallT<Work>;
 
@@ -435,11 +435,10 @@ int siso_run(int device, ssf_siso_params *p, const double *table, void *coef_ino
         if (!rd) return c.rc;
         rdtype = p->ref_dtype;
     }
-    if (!c.ok(hipMemcpyAsync(w.coef.p, coef_inout, coef_bytes, hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
+    if (!c.h2d(w.coef.p, coef_inout, coef_bytes)) return c.rc;
     std::vector<double> &tab = w.host_tab;
     tab.assign(table, table + 2 * (size_t)p->M);
-    if (!c.need(w.tables, tab.size() * sizeof(double))) return c.rc;
-    if (!c.ok(hipMemcpyAsync(w.tables.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
+    if (!c.upload(w.tables, tab)) return c.rc;
 
     if (!reduce_to(c, xd, p->dtype, p->n, 0, false, false, 0)) return c.rc;
     if (p->nref > 0 && !reduce_to(c, rd, rdtype, p->nref, 1, false, false, 0)) return c.rc;
@@ -475,8 +474,7 @@ int siso_run(int device, ssf_siso_params *p, const double *table, void *coef_ino
         k_siso_scale<<<grid_blocks(g.N, kBlock, kMaxBlocks), kBlock, 0, w.st>>>(s, y);
         if (!c.launched()) return c.rc;
     }
-    if (!c.ok(hipMemcpyAsync(coef_inout, w.coef.p, coef_bytes, hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return c.rc;
-    if (!c.deliver(sig_out, y, out_bytes) || !c.deliver(mse_out, mse, mse_bytes)) return c.rc;
+    if (!c.deliver(coef_inout, w.coef.p, coef_bytes) || !c.deliver(sig_out, y, out_bytes) || !c.deliver(mse_out, mse, mse_bytes)) return c.rc;
     if (!c.sync()) return c.rc;
     p->serial_symbols = sp.serial_total, p->parallel_symbols = sp.frozen_count, p->R = sp.serial_total > 0 ? R : 0;
     return SSF_OK;

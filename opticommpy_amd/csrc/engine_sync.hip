@@ -260,13 +260,9 @@ bool run(Call &c, int mode, int nModes, const void *x, int x_dtype, bool x_f32, 
 }
 
 bool fetch_record(Call &c, Record &r, int cols, long long lags) {
-    if (!c.ok(hipMemcpyAsync(&r, c.w->rec.p, sizeof(Record), hipMemcpyDeviceToHost, c.w->st), "hipMemcpy")) return false;
-    if (!c.sync()) return false;
+    if (!c.deliver(&r, c.w->rec.p, sizeof(Record)) || !c.sync()) return false;
     for (int k = 0; k < cols; ++k)
-        if (r.peak_index[k] < 0 || r.peak_index[k] >= lags) {
-            c.rc = SSF_ERR_BAD_ARG, *c.err = "no correlation peak (the input is not finite)";
-            return false;
-        }
+        if (r.peak_index[k] < 0 || r.peak_index[k] >= lags) return c.reject(SSF_ERR_BAD_ARG, "no correlation peak (the input is not finite)");
     return true;
 }
 

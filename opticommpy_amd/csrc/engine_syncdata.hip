@@ -219,9 +219,8 @@ int syncdata_tile(int device, const ssf_sync_tile_params *p, const void *rx, con
     a.rx_out = (Cplx *)c.target(rx_out, w.out, out_bytes);
     a.tx_out = (Cplx *)c.target(tx_out, w.out2, out_bytes);
     if (!a.rx_out || !a.tx_out) return c.rc;
-    a.rx = c.input(rx, w.in, (size_t)p->n_rx * p->nModes * mk::elem_size(p->rx_dtype));
-    a.tx = c.input(tx, w.in2, (size_t)p->n_tx * p->nModes * mk::elem_size(p->tx_dtype));
-    if (!a.rx || !a.tx) return c.rc;
+    if (!(a.rx = c.input(rx, w.in, (size_t)p->n_rx * p->nModes * mk::elem_size(p->rx_dtype)))) return c.rc;
+    if (!(a.tx = c.input(tx, w.in2, (size_t)p->n_tx * p->nModes * mk::elem_size(p->tx_dtype)))) return c.rc;
     k_tile<<<grid_blocks(a.nPad * a.modes, kBlock, kElemMaxBlocks), kBlock, 0, w.st>>>(a);
     if (!c.launched() || !c.deliver(rx_out, a.rx_out, out_bytes) || !c.deliver(tx_out, a.tx_out, out_bytes) || !c.sync()) return c.rc;
     return SSF_OK;
@@ -276,8 +275,7 @@ int syncdata_extract(int device, int64_t n, int modes, int64_t n_out, int out_dt
     k_ext_offsets<<<modes, kBlock, 0, w.st>>>(a);
     k_ext_scatter<<<grid, kBlock, 0, w.st>>>(a);
     if (!c.launched()) return c.rc;
-    if (!c.ok(hipMemcpyAsync(kept, a.off + slots, (size_t)modes * sizeof(int64_t), hipMemcpyDeviceToHost, w.st), "hipMemcpy")) return c.rc;
-    if (!c.deliver(out, a.out, out_bytes) || !c.sync()) return c.rc;
+    if (!c.deliver(kept, a.off + slots, (size_t)modes * sizeof(int64_t)) || !c.deliver(out, a.out, out_bytes) || !c.sync()) return c.rc;
     return SSF_OK;
 }
 
@@ -307,9 +305,8 @@ int syncdata_bert(int device, int64_t n, const void *irx, const void *bits, doub
     BertArgs a{};
     a.n = n, a.nb = grid_blocks(n, kBlock, kBertMaxBlocks);
     if (!c.need(w.part, (size_t)a.nb * 3 * sizeof(double)) || !c.need(w.scal, kBertScal * sizeof(double))) return c.rc;
-    a.x = (const double *)c.input(irx, w.in, (size_t)n * sizeof(double));
-    a.bits = (const uint8_t *)c.input(bits, w.in2, (size_t)n);
-    if (!a.x || !a.bits) return c.rc;
+    if (!(a.x = (const double *)c.input(irx, w.in, (size_t)n * sizeof(double)))) return c.rc;
+    if (!(a.bits = (const uint8_t *)c.input(bits, w.in2, (size_t)n))) return c.rc;
     a.part = (double *)w.part.p, a.scal = (double *)w.scal.p;
     k_bert_stats<<<a.nb, kBlock, 0, w.st>>>(a);
     k_bert_fin<<<1, 64, 0, w.st>>>(a, 0);
@@ -318,7 +315,7 @@ int syncdata_bert(int device, int64_t n, const void *irx, const void *bits, doub
     k_bert_errors<<<a.nb, kBlock, 0, w.st>>>(a);
     k_bert_fin<<<1, 64, 0, w.st>>>(a, 2);
     if (!c.launched()) return c.rc;
-    if (!c.ok(hipMemcpyAsync(scal_out, a.scal, kBertScal * sizeof(double), hipMemcpyDeviceToHost, w.st), "hipMemcpy") || !c.sync()) return c.rc;
+    if (!c.deliver(scal_out, a.scal, kBertScal * sizeof(double)) || !c.sync()) return c.rc;
     return SSF_OK;
 }
 

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(64) void k_calc_fin(CArgs a) {
 
 struct Work : WorkBase {
     Buf tables, part, res, in_rx, in_tx;
-    std::vector<double> host_tab;              // source of an asynchronous upload: it outlives the call
+    std::vector<double> host_tab;              // kept for its capacity
 };
 using Call = CallT<Work>;
 
@@ -88,15 +88,13 @@ int theory_mi(int device, int M, int nS, const double *const_tab, const double *
     if (c.rc) return c.rc;
     Work &w = *c.w;
     std::vector<double> &tab = w.host_tab;
-    if (!c.sync()) return c.rc;                // an upload of a call that failed before its own wait may still read host_tab
     tab.assign(const_tab, const_tab + 2 * (size_t)M);
     tab.insert(tab.end(), px, px + M);
     tab.insert(tab.end(), sigma, sigma + nS);
     const int chunk = std::max(1, std::min(nS, kRowsPerLaunch / M));
-    if (!c.need(w.tables, tab.size() * sizeof(double))) return c.rc;
+    if (!c.upload(w.tables, tab)) return c.rc;
     if (!c.need(w.part, (size_t)chunk * M * kTiles * 2 * sizeof(double))) return c.rc;
     if (!c.need(w.res, (size_t)nS * sizeof(double))) return c.rc;
-    if (!c.ok(hipMemcpyAsync(w.tables.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
     TArgs a{};
     a.tab = (const double *)w.tables.p, a.px = a.tab + 2 * M, a.sigma = a.px + M;
     a.part = (double *)w.part.p, a.res = (double *)w.res.p, a.M = M;
@@ -120,20 +118,18 @@ int theory_calc_mi(int device, int64_t n, int dtype, int M, double sigma2, const
     if (c.rc) return c.rc;
     Work &w = *c.w;
     std::vector<double> &tab = w.host_tab;     // table (2M) | px (M) | log2 px (M)
-    if (!c.sync()) return c.rc;                // as in theory_mi
     tab.assign(const_tab, const_tab + 2 * (size_t)M);
     tab.insert(tab.end(), px, px + M);
     for (int m = 0; m < M; ++m) tab.push_back(std::log2(px[m]));
     CArgs a{};
     a.n = n, a.M = M, a.dtype = dtype, a.nb = grid_blocks(n, kBlock, kMaxBlocks);
     a.ninv = -(1.0 / sigma2), a.H = entropy(px, M);
-    if (!c.need(w.tables, tab.size() * sizeof(double))) return c.rc;
+    if (!c.upload(w.tables, tab)) return c.rc;
     if (!c.need(w.part, (size_t)kMaxBlocks * sizeof(double))) return c.rc;
     if (!c.need(w.res, sizeof(double))) return c.rc;
     const size_t in_bytes = (size_t)n * mk::elem_size(dtype);
     if (!(a.rx = c.input(rx, w.in_rx, in_bytes))) return c.rc;
     if (!(a.tx = c.input(tx, w.in_tx, in_bytes))) return c.rc;
-    if (!c.ok(hipMemcpyAsync(w.tables.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, w.st), "hipMemcpy")) return c.rc;
     a.tab = (const double *)w.tables.p, a.px = a.tab + 2 * M, a.log2px = a.tab + 3 * M;
     a.part = (double *)w.part.p, a.res = (double *)w.res.p;
     k_calc_mi<<<a.nb, kBlock, 4 * (size_t)M * sizeof(double), w.st>>>(a);

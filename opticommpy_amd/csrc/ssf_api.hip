@@ -16,6 +16,25 @@ int set_err(int code, const std::string &m) {
     return code;
 }
 
+int check_device(int device) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_err(SSF_ERR_NO_DEVICE, "no HIP device visible");
+    if (device < 0 || device >= ndev) return set_err(SSF_ERR_NO_DEVICE, "device index out of range");
+    return SSF_OK;
+}
+
+// the tail of an entry point that goes into an engine: run(err) is the engine's function, its text goes out as "<name>: <text>"
+template <class F> int engine_result(const char *name, F &&run) {
+    std::string err;
+    const int rc = run(&err);
+    return rc ? set_err(rc, std::string(name) + ": " + err) : SSF_OK;
+}
+// ... after the device index has been checked
+template <class F> int engine_call(const char *name, int device, F &&run) {
+    if (int rc = check_device(device)) return rc;
+    return engine_result(name, run);
+}
+
 int check_params(ssf_plan *pl, const ssf_params *p, int s0, int s1) {
     if (!p) return fail(pl, SSF_ERR_BAD_ARG, "params is NULL");
     if (p->model != SSF_MODEL_NLSE && p->model != SSF_MODEL_MANAKOV) return fail(pl, SSF_ERR_BAD_ARG, "bad model");
@@ -310,9 +329,8 @@ int ssf_set_coupling_comm(ssf_plan *plan, ssf_comm *comm) {
     return rc ? fail(plan, rc, "device-side coupling needs the device-resident fused pipeline (else: ssf_set_coupling on SSF_ENGINE_ROCFFT)") : SSF_OK;
 }
 
-static int rx_check_device(int device);
 int ssf_couple_reduce_selftest(int device, int32_t nranks, int32_t npart, const double *parts, double *out5) {
-    if (int rc = rx_check_device(device)) return rc;
+    if (int rc = check_device(device)) return rc;
     if (hipSetDevice(device) != hipSuccess) return set_err(SSF_ERR_HIP, "hipSetDevice");
     std::string err;
     int rc = ssf::fused_couple_reduce_selftest(nranks, npart, parts, out5, &err);
@@ -551,96 +569,67 @@ int ssf_device_memcpy(int device, void *dst, const void *src, int64_t bytes) {
 }
 
 // ---- receiver side (engine_rx.hip) -----------------------------------------------------------
-static int rx_check_device(int device) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return set_err(SSF_ERR_NO_DEVICE, "no HIP device visible");
-    if (device < 0 || device >= ndev) return set_err(SSF_ERR_NO_DEVICE, "device index out of range");
-    return SSF_OK;
-}
-
 int ssf_fir_filter(int device, int64_t sigLen, int32_t ncols, int32_t ntaps, const void *taps, const void *in, void *out) {
     if (!taps || !in || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_fir_filter: NULL argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::rx_fir(device, sigLen, ncols, ntaps, taps, in, out, &err);
-    return rc ? set_err(rc, "ssf_fir_filter: " + err) : SSF_OK;
+    return engine_call("ssf_fir_filter", device, [&](std::string *err) { return ssf::rx_fir(device, sigLen, ncols, ntaps, taps, in, out, err); });
 }
 
 int ssf_fir_long(int device, int64_t inLen, int64_t outLen, int32_t ncols, int64_t ntaps, const void *taps, int64_t shift,
                  const void *in, void *out) {
     if (!taps || !in || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_fir_long: NULL argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::rx_fir_long(device, inLen, outLen, ncols, ntaps, taps, shift, in, out, &err);
-    return rc ? set_err(rc, "ssf_fir_long: " + err) : SSF_OK;
+    return engine_call("ssf_fir_long", device, [&](std::string *err) { return ssf::rx_fir_long(device, inLen, outLen, ncols, ntaps, taps, shift, in, out, err); });
 }
 
 int ssf_device_axpy(int device, int64_t n, double alpha, const double *x, double *y) {
     if (!x || !y) return set_err(SSF_ERR_BAD_ARG, "ssf_device_axpy: NULL argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::rx_axpy(device, n, alpha, x, y, &err);
-    return rc ? set_err(rc, "ssf_device_axpy: " + err) : SSF_OK;
+    return engine_call("ssf_device_axpy", device, [&](std::string *err) { return ssf::rx_axpy(device, n, alpha, x, y, err); });
 }
 
 int ssf_delay_signal(int device, int64_t N, double delay, double Fs, const void *in, void *out) {
     if (!in || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_delay_signal: NULL argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::rx_delay(device, N, delay, Fs, in, out, &err);
-    return rc ? set_err(rc, "ssf_delay_signal: " + err) : SSF_OK;
+    return engine_call("ssf_delay_signal", device, [&](std::string *err) { return ssf::rx_delay(device, N, delay, Fs, in, out, err); });
 }
 
 int ssf_edfa(int device, int64_t n, int32_t ncols, double G_lin, double p_noise, int64_t rng_seed, int32_t rng_row_offset,
              const void *field_in, const void *noise, void *field_out) {
     if (!field_in || !field_out || n < 1 || ncols < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_edfa: bad argument");
     if (!(G_lin > 0) || p_noise < 0) return set_err(SSF_ERR_BAD_ARG, "ssf_edfa: the gain must be positive, the noise power non-negative");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
     const double sigma = (!noise && rng_seed != 0) ? std::sqrt(p_noise / 2) : 0.0;                  // core.py:739-763
-    int rc = ssf::rx_optics(device, ssf::kOptEdfa, n, ncols, std::sqrt(G_lin), sigma, (unsigned long long)rng_seed,
-                            (unsigned)rng_row_offset, field_in, noise, field_out, nullptr, &err);
-    return rc ? set_err(rc, "ssf_edfa: " + err) : SSF_OK;
+    return engine_call("ssf_edfa", device, [&](std::string *err) {
+        return ssf::rx_optics(device, ssf::kOptEdfa, n, ncols, std::sqrt(G_lin), sigma, (unsigned long long)rng_seed,
+                              (unsigned)rng_row_offset, field_in, noise, field_out, nullptr, err);
+    });
 }
 
 int ssf_pbs(int device, int64_t N, int32_t ncols, double theta, const void *E, void *Ex, void *Ey) {
     if (!E || !Ex || !Ey || N < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_pbs: bad argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::rx_optics(device, ssf::kOptPbs, N, ncols, std::cos(theta), std::sin(theta), 0, 0, E, nullptr, Ex, Ey, &err);
-    return rc ? set_err(rc, "ssf_pbs: " + err) : SSF_OK;
+    return engine_call("ssf_pbs", device, [&](std::string *err) {
+        return ssf::rx_optics(device, ssf::kOptPbs, N, ncols, std::cos(theta), std::sin(theta), 0, 0, E, nullptr, Ex, Ey, err);
+    });
 }
 
 int ssf_optical_hybrid_2x4(int device, int64_t N, const void *Es, const void *Elo, void *Eo) {
     if (!Es || !Elo || !Eo || N < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_optical_hybrid_2x4: bad argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::rx_optics(device, ssf::kOptHybrid, N, 1, 0.0, 0.0, 0, 0, Es, Elo, Eo, nullptr, &err);
-    return rc ? set_err(rc, "ssf_optical_hybrid_2x4: " + err) : SSF_OK;
+    return engine_call("ssf_optical_hybrid_2x4", device, [&](std::string *err) {
+        return ssf::rx_optics(device, ssf::kOptHybrid, N, 1, 0.0, 0.0, 0, 0, Es, Elo, Eo, nullptr, err);
+    });
 }
 
 int ssf_nlin_phase_rot(int device, int64_t n, double gamma, const void *Ex, const void *Ey, const double *Pch, double *phi) {
     if (!Ex || !Ey || !Pch || !phi) return set_err(SSF_ERR_BAD_ARG, "ssf_nlin_phase_rot: NULL argument");
-    std::string err;
-    const int rc = mk_nlin_phase(device, n, gamma, Ex, Ey, Pch, phi, &err);
-    return rc ? set_err(rc, "ssf_nlin_phase_rot: " + err) : SSF_OK;
+    return engine_result("ssf_nlin_phase_rot", [&](std::string *err) { return mk_nlin_phase(device, n, gamma, Ex, Ey, Pch, phi, err); });
 }
 
 int ssf_convergence_condition(int device, int64_t n, const void *Ex_fd, const void *Ey_fd, const void *Ex_conv,
                               const void *Ey_conv, double *lim) {
     if (!Ex_fd || !Ey_fd || !Ex_conv || !Ey_conv || !lim) return set_err(SSF_ERR_BAD_ARG, "ssf_convergence_condition: NULL argument");
-    std::string err;
-    const int rc = mk_convergence(device, n, Ex_fd, Ey_fd, Ex_conv, Ey_conv, lim, &err);
-    return rc ? set_err(rc, "ssf_convergence_condition: " + err) : SSF_OK;
+    return engine_result("ssf_convergence_condition", [&](std::string *err) { return mk_convergence(device, n, Ex_fd, Ey_fd, Ex_conv, Ey_conv, lim, err); });
 }
 
 int ssf_decimate(int device, int64_t N, int32_t ncols, int32_t SpSin, int32_t decFactor, const void *in, void *out,
                  int32_t *sampDelay) {
     if (!in || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_decimate: NULL argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::rx_decimate(device, N, ncols, SpSin, decFactor, in, out, sampDelay, &err);
-    return rc ? set_err(rc, "ssf_decimate: " + err) : SSF_OK;
+    return engine_call("ssf_decimate", device, [&](std::string *err) { return ssf::rx_decimate(device, N, ncols, SpSin, decFactor, in, out, sampDelay, err); });
 }
 
 int ssf_rx_run(int device, int32_t mode, int64_t N, int32_t nmodes, const ssf_rx_params *params, const void *in0,
@@ -648,29 +637,22 @@ int ssf_rx_run(int device, int32_t mode, int64_t N, int32_t nmodes, const ssf_rx
     if (!params || !in0 || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_rx_run: NULL argument");
     if (mode < SSF_RX_PHOTODIODE || mode > SSF_RX_IQ_MIXING) return set_err(SSF_ERR_BAD_ARG, "ssf_rx_run: unknown mode");
     if ((mode == SSF_RX_COHERENT || mode == SSF_RX_PDM_COHERENT) && !lo) return set_err(SSF_ERR_BAD_ARG, "ssf_rx_run: the LO field is NULL");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::rx_run(device, mode, N, nmodes, params, in0, lo, unit_normals, out, &err);
-    return rc ? set_err(rc, "ssf_rx_run: " + err) : SSF_OK;
+    return engine_call("ssf_rx_run", device, [&](std::string *err) { return ssf::rx_run(device, mode, N, nmodes, params, in0, lo, unit_normals, out, err); });
 }
 
 int ssf_rx_chain(int device, int64_t N, const ssf_rx_params *params, const void *Es, const void *Elo, const void *taps, int32_t ntaps,
                  int32_t SpSin, int32_t decFactor, const void *edc_Hfft, int32_t edc_K, int32_t edc_nfft, void *sig_out,
                  int32_t *sampDelay) {
     if (!params || !Es || !Elo || !taps || !edc_Hfft || !sig_out) return set_err(SSF_ERR_BAD_ARG, "ssf_rx_chain: NULL argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::rx_chain(device, N, params, Es, Elo, taps, ntaps, SpSin, decFactor, edc_Hfft, edc_K, edc_nfft, sig_out, sampDelay, &err);
-    return rc ? set_err(rc, "ssf_rx_chain: " + err) : SSF_OK;
+    return engine_call("ssf_rx_chain", device, [&](std::string *err) {
+        return ssf::rx_chain(device, N, params, Es, Elo, taps, ntaps, SpSin, decFactor, edc_Hfft, edc_K, edc_nfft, sig_out, sampDelay, err);
+    });
 }
 
 int ssf_wdm_tx(int device, const ssf_tx_params *params, const void *symbols, const double *taps, const double *phi,
                const double *amp, const double *deltaF, void *sig_out, double *power_out) {
     if (!params || !symbols || !taps || !amp || !deltaF || !sig_out) return set_err(SSF_ERR_BAD_ARG, "ssf_wdm_tx: NULL argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::tx_wdm(device, params, symbols, taps, phi, amp, deltaF, sig_out, power_out, &err);
-    return rc ? set_err(rc, "ssf_wdm_tx: " + err) : SSF_OK;
+    return engine_call("ssf_wdm_tx", device, [&](std::string *err) { return ssf::tx_wdm(device, params, symbols, taps, phi, amp, deltaF, sig_out, power_out, err); });
 }
 
 // ---- IM/DD transmitter and AWGN channel (engine_rx.hip, imddtx_kernels.h): every check comes before the first allocation or launch
@@ -684,11 +666,11 @@ int ssf_pam_tx(int device, int64_t nSymbols, int32_t SpS, int32_t nPolModes, int
     if (nSymbols > (int64_t)1 << 40 || nSymbols * SpS > (int64_t)1 << 40) return set_err(SSF_ERR_BAD_ARG, "ssf_pam_tx: too many samples");
     if (!(Vpi != 0) || !std::isfinite(Vpi) || !std::isfinite(Vb) || !std::isfinite(ER) || !std::isfinite(mzmScale) || !std::isfinite(amp))
         return set_err(SSF_ERR_BAD_ARG, "ssf_pam_tx: Vpi must be non-zero and every modulator parameter finite");
-    if (int rc = rx_check_device(device)) return rc;
+    if (int rc = check_device(device)) return rc;
     if (ssf::on_device(symbols) || ssf::on_device(taps)) return set_err(SSF_ERR_BAD_ARG, "ssf_pam_tx: symbols and taps are host arrays");
-    std::string err;
-    int rc = ssf::tx_pam(device, nSymbols, SpS, nPolModes, ntaps, symbols, taps, mzmScale, Vpi, Vb, ER, amp, sig_out, &err);
-    return rc ? set_err(rc, "ssf_pam_tx: " + err) : SSF_OK;
+    return engine_result("ssf_pam_tx", [&](std::string *err) {
+        return ssf::tx_pam(device, nSymbols, SpS, nPolModes, ntaps, symbols, taps, mzmScale, Vpi, Vb, ER, amp, sig_out, err);
+    });
 }
 
 int ssf_modulate_optical(int device, int32_t kind, int64_t n, int32_t u_dtype, const void *u, const void *Ei, double Ei_re, double Ei_im,
@@ -698,10 +680,9 @@ int ssf_modulate_optical(int device, int32_t kind, int64_t n, int32_t u_dtype, c
     if (n < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate_optical: n must be at least 1");
     if (!tx_real_or_complex(u_dtype)) return set_err(SSF_ERR_UNSUPPORTED, "ssf_modulate_optical: the drive is float64 or complex128");
     if (!(Vpi != 0) || !std::isfinite(Vpi)) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate_optical: Vpi must be finite and non-zero");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::tx_modulate(device, kind, n, u_dtype == SSF_M_C128, u, Ei, Ei_re, Ei_im, Vpi, VbI, VbQ, Vphi, ERI, ERQ, out, &err);
-    return rc ? set_err(rc, "ssf_modulate_optical: " + err) : SSF_OK;
+    return engine_call("ssf_modulate_optical", device, [&](std::string *err) {
+        return ssf::tx_modulate(device, kind, n, u_dtype == SSF_M_C128, u, Ei, Ei_re, Ei_im, Vpi, VbI, VbQ, Vphi, ERI, ERQ, out, err);
+    });
 }
 
 int ssf_awgn(int device, int64_t n, int32_t ncols, int32_t in_dtype, int32_t out_dtype, int32_t complex_noise, double Fs_over_B,
@@ -714,11 +695,10 @@ int ssf_awgn(int device, int64_t n, int32_t ncols, int32_t in_dtype, int32_t out
     if (!(Fs_over_B > 0) || !std::isfinite(Fs_over_B)) return set_err(SSF_ERR_BAD_ARG, "ssf_awgn: Fs / B must be positive and finite");
     if (!(snr_lin > 0) || !std::isfinite(snr_lin)) return set_err(SSF_ERR_BAD_ARG, "ssf_awgn: the linear SNR must be positive and finite");
     if (!unit_normals && rng_seed == 0) return set_err(SSF_ERR_BAD_ARG, "ssf_awgn: unit normals or a non-zero rng_seed");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::ch_awgn(device, n, ncols, in_dtype == SSF_M_C128, out_dtype == SSF_M_C128, complex_noise != 0, Fs_over_B, snr_lin, sig_in,
-                          unit_normals, (unsigned long long)rng_seed, sig_out, &err);
-    return rc ? set_err(rc, "ssf_awgn: " + err) : SSF_OK;
+    return engine_call("ssf_awgn", device, [&](std::string *err) {
+        return ssf::ch_awgn(device, n, ncols, in_dtype == SSF_M_C128, out_dtype == SSF_M_C128, complex_noise != 0, Fs_over_B, snr_lin,
+                            sig_in, unit_normals, (unsigned long long)rng_seed, sig_out, err);
+    });
 }
 
 int ssf_upsample(int device, int64_t rows, int32_t w, int32_t factor, double scale, const void *in, void *out) {
@@ -727,10 +707,7 @@ int ssf_upsample(int device, int64_t rows, int32_t w, int32_t factor, double sca
     if (factor < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_upsample: the factor must be at least 1");
     if (!std::isfinite(scale)) return set_err(SSF_ERR_BAD_ARG, "ssf_upsample: the scale must be finite");
     if (in == out && factor > 1) return set_err(SSF_ERR_BAD_ARG, "ssf_upsample: in place only with factor 1");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::tx_stuff(device, rows, w, factor, scale, in, out, &err);
-    return rc ? set_err(rc, "ssf_upsample: " + err) : SSF_OK;
+    return engine_call("ssf_upsample", device, [&](std::string *err) { return ssf::tx_stuff(device, rows, w, factor, scale, in, out, err); });
 }
 
 // ---- link metrics (engine_metrics.hip): every check comes before the first allocation or launch
@@ -753,37 +730,25 @@ int ssf_metrics(int device, const ssf_metrics_params *p, const void *rx, const v
         if (!tx || !const_raw) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: tx or const_raw is NULL");
         if (!(p->Es > 0) || !(p->H > 0)) return set_err(SSF_ERR_BAD_ARG, "ssf_metrics: Es and H must be positive");
     }
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::metrics_run(device, p, rx, tx, const_raw, const_norm, px, evm_w32, out, &err);
-    return rc ? set_err(rc, "ssf_metrics: " + err) : SSF_OK;
+    return engine_call("ssf_metrics", device, [&](std::string *err) { return ssf::metrics_run(device, p, rx, tx, const_raw, const_norm, px, evm_w32, out, err); });
 }
 
 int ssf_pnorm(int device, int64_t count, int32_t dtype, const void *x, void *y) {
     if (!x || !y || count < 1 || metrics_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_pnorm: bad argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::metrics_pnorm(device, count, dtype, x, y, &err);
-    return rc ? set_err(rc, "ssf_pnorm: " + err) : SSF_OK;
+    return engine_call("ssf_pnorm", device, [&](std::string *err) { return ssf::metrics_pnorm(device, count, dtype, x, y, err); });
 }
 
 int ssf_signal_power(int device, int64_t count, int64_t rows, int32_t dtype, const void *x, double *out) {
     if (!x || !out || count < 1 || rows < 1 || count % rows || metrics_bad_dtype(dtype))
         return set_err(SSF_ERR_BAD_ARG, "ssf_signal_power: bad argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::metrics_power(device, count, rows, dtype, x, out, &err);
-    return rc ? set_err(rc, "ssf_signal_power: " + err) : SSF_OK;
+    return engine_call("ssf_signal_power", device, [&](std::string *err) { return ssf::metrics_power(device, count, rows, dtype, x, out, err); });
 }
 
 int ssf_demodulate(int device, int64_t count, int32_t dtype, int32_t M, const double *const_raw, const void *symb,
                    int32_t *bits_out) {
     if (!const_raw || !symb || !bits_out || count < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_demodulate: bad argument");
     if (metrics_bad_M(M) || metrics_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_demodulate: bad M or dtype");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::metrics_demod(device, count, dtype, M, const_raw, symb, bits_out, &err);
-    return rc ? set_err(rc, "ssf_demodulate: " + err) : SSF_OK;
+    return engine_call("ssf_demodulate", device, [&](std::string *err) { return ssf::metrics_demod(device, count, dtype, M, const_raw, symb, bits_out, err); });
 }
 
 // ---- theoretical and Monte-Carlo mutual information (engine_theory.hip): every check comes before the first allocation or launch
@@ -806,10 +771,7 @@ int ssf_theory_mi(int device, int32_t M, int32_t nS, const double *const_tab, co
     if (theory_bad_px(px, M)) return set_err(SSF_ERR_BAD_ARG, "ssf_theory_mi: px must be finite and positive");
     for (int s = 0; s < nS; ++s)
         if (!(sigma[s] > 0) || !std::isfinite(sigma[s])) return set_err(SSF_ERR_BAD_ARG, "ssf_theory_mi: sigma must be finite and positive");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::theory_mi(device, M, nS, const_tab, px, sigma, mi_out, &err);
-    return rc ? set_err(rc, "ssf_theory_mi: " + err) : SSF_OK;
+    return engine_call("ssf_theory_mi", device, [&](std::string *err) { return ssf::theory_mi(device, M, nS, const_tab, px, sigma, mi_out, err); });
 }
 
 int ssf_calc_mi(int device, int64_t n, int32_t dtype, int32_t M, double sigma2, const double *const_tab, const double *px, const void *rx,
@@ -820,10 +782,7 @@ int ssf_calc_mi(int device, int64_t n, int32_t dtype, int32_t M, double sigma2, 
     if (!(sigma2 > 0) || !std::isfinite(sigma2)) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_mi: sigma2 must be finite and positive");
     if (theory_bad_table(const_tab, M)) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_mi: the table must be finite");
     if (theory_bad_px(px, M)) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_mi: px must be finite and positive");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::theory_calc_mi(device, n, dtype, M, sigma2, const_tab, px, rx, tx, mi_out, &err);
-    return rc ? set_err(rc, "ssf_calc_mi: " + err) : SSF_OK;
+    return engine_call("ssf_calc_mi", device, [&](std::string *err) { return ssf::theory_calc_mi(device, n, dtype, M, sigma2, const_tab, px, rx, tx, mi_out, err); });
 }
 
 // ---- carrier phase recovery (engine_cpr.hip): every check comes before the first allocation or launch
@@ -847,10 +806,7 @@ int ssf_cpr(int device, const ssf_cpr_params *p, const double *const_tab, const 
     if (const char *m = cpr_bad_shape(p->n, p->nModes, p->dtype)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_cpr: ") + m);
     if (const char *m = cpr_bad_search(p->Nh, p->B, p->M)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_cpr: ") + m);
     if (p->runFOE && cpr_bad_foe(p->P, p->Fs)) return set_err(SSF_ERR_BAD_ARG, "ssf_cpr: P must be 1 .. 1024 and Fs positive");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::cpr_run(device, p, const_tab, x, sig_out, phase_out, fo_out, &err);
-    return rc ? set_err(rc, "ssf_cpr: " + err) : SSF_OK;
+    return engine_call("ssf_cpr", device, [&](std::string *err) { return ssf::cpr_run(device, p, const_tab, x, sig_out, phase_out, fo_out, err); });
 }
 
 int ssf_bps(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t Nh, int32_t B, int32_t M, const double *const_tab,
@@ -858,10 +814,7 @@ int ssf_bps(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t Nh, in
     if (!const_tab || !x || !phase_out) return set_err(SSF_ERR_BAD_ARG, "ssf_bps: NULL argument");
     if (const char *m = cpr_bad_shape(n, nModes, dtype)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_bps: ") + m);
     if (const char *m = cpr_bad_search(Nh, B, M)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_bps: ") + m);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::cpr_bps(device, n, nModes, dtype, Nh, B, M, const_tab, x, phase_out, &err);
-    return rc ? set_err(rc, "ssf_bps: " + err) : SSF_OK;
+    return engine_call("ssf_bps", device, [&](std::string *err) { return ssf::cpr_bps(device, n, nModes, dtype, Nh, B, M, const_tab, x, phase_out, err); });
 }
 
 int ssf_foe(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t P, double Fs, const void *x, void *sig_out,
@@ -869,10 +822,7 @@ int ssf_foe(int device, int64_t n, int32_t nModes, int32_t dtype, int32_t P, dou
     if (!x || !sig_out || !fo_out) return set_err(SSF_ERR_BAD_ARG, "ssf_foe: NULL argument");
     if (const char *m = cpr_bad_shape(n, nModes, dtype)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_foe: ") + m);
     if (cpr_bad_foe(P, Fs)) return set_err(SSF_ERR_BAD_ARG, "ssf_foe: P must be 1 .. 1024 and Fs positive");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::cpr_foe(device, n, nModes, dtype, P, Fs, x, sig_out, fo_out, &err);
-    return rc ? set_err(rc, "ssf_foe: " + err) : SSF_OK;
+    return engine_call("ssf_foe", device, [&](std::string *err) { return ssf::cpr_foe(device, n, nModes, dtype, P, Fs, x, sig_out, fo_out, err); });
 }
 
 // ---- sequence synchronisation (engine_sync.hip)
@@ -886,10 +836,7 @@ int ssf_symbol_sync(int device, const ssf_sync_params *p, const void *rx, const 
     if (p->n_tx > (1LL << 31) || p->n_rx > (1LL << 31)) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: at most 2^31 rows");
     for (int32_t d : {p->rx_dtype, p->tx_dtype})
         if (d != SSF_M_C128 && d != SSF_M_C64) return set_err(SSF_ERR_BAD_ARG, "ssf_symbol_sync: dtype must be complex128 or complex64");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::sync_run(device, p, rx, tx, out, result, &err);
-    return rc ? set_err(rc, "ssf_symbol_sync: " + err) : SSF_OK;
+    return engine_call("ssf_symbol_sync", device, [&](std::string *err) { return ssf::sync_run(device, p, rx, tx, out, result, err); });
 }
 
 int ssf_finddelay(int device, int64_t nx, int64_t ny, int32_t x_dtype, int32_t y_dtype, const void *x, const void *y, int64_t *delay_out) {
@@ -897,10 +844,7 @@ int ssf_finddelay(int device, int64_t nx, int64_t ny, int32_t x_dtype, int32_t y
     if (nx < 1 || ny < 1 || nx > (1LL << 31) || ny > (1LL << 31)) return set_err(SSF_ERR_BAD_ARG, "ssf_finddelay: lengths must be 1 .. 2^31");
     for (int32_t d : {x_dtype, y_dtype})
         if (d < SSF_M_C128 || d > SSF_M_F32) return set_err(SSF_ERR_BAD_ARG, "ssf_finddelay: unknown dtype");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::sync_finddelay(device, nx, ny, x_dtype, y_dtype, x, y, delay_out, &err);
-    return rc ? set_err(rc, "ssf_finddelay: " + err) : SSF_OK;
+    return engine_call("ssf_finddelay", device, [&](std::string *err) { return ssf::sync_finddelay(device, nx, ny, x_dtype, y_dtype, x, y, delay_out, err); });
 }
 
 int ssf_sync_transform_time(int device, int64_t L, int32_t nseq, int32_t nslots, int32_t nslots2, int32_t reps, double *seconds_out) {
@@ -908,10 +852,9 @@ int ssf_sync_transform_time(int device, int64_t L, int32_t nseq, int32_t nslots,
     if (L < 4 || L > (1LL << 32) || (L & (L - 1))) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_transform_time: L must be a power of two, 4 .. 2^32");
     if (nseq < 1 || nseq > 24 || nslots < 1 || nslots > 64 || nslots2 < 0 || nslots2 > nslots || reps < 1 || reps > 1000)
         return set_err(SSF_ERR_BAD_ARG, "ssf_sync_transform_time: 1 <= nseq <= 24, 0 <= nslots2 <= nslots <= 64, 1 <= reps <= 1000");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::sync_transform_time(device, L, nseq, nslots, nslots2, reps, seconds_out, &err);
-    return rc ? set_err(rc, "ssf_sync_transform_time: " + err) : SSF_OK;
+    return engine_call("ssf_sync_transform_time", device, [&](std::string *err) {
+        return ssf::sync_transform_time(device, L, nseq, nslots, nslots2, reps, seconds_out, err);
+    });
 }
 
 // ---- adaptive MIMO equalizer (engine_eq.hip): every check comes before the first allocation or launch
@@ -946,10 +889,9 @@ int ssf_mimo_eq(int device, const ssf_eq_params *p, const ssf_eq_stage *stages, 
                 void *H_inout, const void *x, const void *ref, void *sig_out, double *errsq_out) {
     if (!p || !stages || !const_tab || !radii_tab || !H_inout || !x || !sig_out) return set_err(SSF_ERR_BAD_ARG, "ssf_mimo_eq: NULL argument");
     if (const char *m = eq_bad(p, stages, ref)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_mimo_eq: ") + m);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::eq_run(device, p, stages, const_tab, radii_tab, H_inout, x, ref, sig_out, errsq_out, &err);
-    return rc ? set_err(rc, "ssf_mimo_eq: " + err) : SSF_OK;
+    return engine_call("ssf_mimo_eq", device, [&](std::string *err) {
+        return ssf::eq_run(device, p, stages, const_tab, radii_tab, H_inout, x, ref, sig_out, errsq_out, err);
+    });
 }
 
 // ---- ffe, dfe, volterra, anorm (engine_siso.hip): every check comes before the first allocation or launch
@@ -993,10 +935,7 @@ int ssf_siso_eq(int device, ssf_siso_params *p, const double *const_tab, void *c
     if (!p || !x || !sig_out) return set_err(SSF_ERR_BAD_ARG, "ssf_siso_eq: NULL argument");
     if (const char *m = siso_bad(p, ref)) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_siso_eq: ") + m);
     if (p->kind != SSF_SISO_ANORM && (!const_tab || !coef_inout || !mse_out)) return set_err(SSF_ERR_BAD_ARG, "ssf_siso_eq: NULL argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::siso_run(device, p, const_tab, coef_inout, x, ref, sig_out, mse_out, &err);
-    return rc ? set_err(rc, "ssf_siso_eq: " + err) : SSF_OK;
+    return engine_call("ssf_siso_eq", device, [&](std::string *err) { return ssf::siso_run(device, p, const_tab, coef_inout, x, ref, sig_out, mse_out, err); });
 }
 
 // ---- mlse, detector, autocorr (engine_seqdet.hip): every check comes before the first allocation or launch
@@ -1014,10 +953,7 @@ int ssf_mlse(int device, ssf_mlse_params *p, const double *h, const double *cons
     const int64_t bytes = ssf::mlse_survivor_bytes(p->n, p->cols, p->M, p->taps);
     if (bytes > ((int64_t)1 << 31))
         return set_err(SSF_ERR_BAD_ARG, "ssf_mlse: survivor memory of " + std::to_string(bytes) + " bytes is above 2^31 bytes");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::mlse_run(device, p, h, const_tab, y, out, final_metric, &err);
-    return rc ? set_err(rc, "ssf_mlse: " + err) : SSF_OK;
+    return engine_call("ssf_mlse", device, [&](std::string *err) { return ssf::mlse_run(device, p, h, const_tab, y, out, final_metric, err); });
 }
 
 int ssf_detector(int device, int64_t n, int32_t dtype, int32_t M, int32_t rule, double sigma2, const double *const_tab, const double *logpx,
@@ -1029,20 +965,16 @@ int ssf_detector(int device, int64_t n, int32_t dtype, int32_t M, int32_t rule, 
     if (M < 1 || M > 64) return set_err(SSF_ERR_BAD_ARG, "ssf_detector: M must be 1 .. 64");
     if (n < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_detector: n must be at least 1");
     if (rule == SSF_DET_MAP && !(sigma2 > 0)) return set_err(SSF_ERR_BAD_ARG, "ssf_detector: sigma2 must be positive");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::detector_run(device, n, dtype, M, rule, sigma2, const_tab, logpx, r, decided, ind, &err);
-    return rc ? set_err(rc, "ssf_detector: " + err) : SSF_OK;
+    return engine_call("ssf_detector", device, [&](std::string *err) {
+        return ssf::detector_run(device, n, dtype, M, rule, sigma2, const_tab, logpx, r, decided, ind, err);
+    });
 }
 
 int ssf_autocorr(int device, int64_t n, int32_t nTaps, const void *x, double *r_out) {
     if (!x || !r_out) return set_err(SSF_ERR_BAD_ARG, "ssf_autocorr: NULL argument");
     if (nTaps < 1 || nTaps > 256) return set_err(SSF_ERR_BAD_ARG, "ssf_autocorr: nTaps must be 1 .. 256");
     if (n < nTaps) return set_err(SSF_ERR_BAD_ARG, "ssf_autocorr: nTaps exceeds n");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::autocorr_run(device, n, nTaps, x, r_out, &err);
-    return rc ? set_err(rc, "ssf_autocorr: " + err) : SSF_OK;
+    return engine_call("ssf_autocorr", device, [&](std::string *err) { return ssf::autocorr_run(device, n, nTaps, x, r_out, err); });
 }
 
 // ---- syncDataSequences' glue, movingAverage, bert (engine_syncdata.hip): every check comes before the first allocation or launch
@@ -1053,10 +985,7 @@ int ssf_sync_tile(int device, const ssf_sync_tile_params *p, const void *rx, con
     if (p->n_pad < p->n_rx || p->n_pad > (1LL << 31)) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_tile: n_rx <= n_pad <= 2^31");
     for (int32_t d : {p->rx_dtype, p->tx_dtype})
         if (d != SSF_M_C128 && d != SSF_M_C64 && d != SSF_M_F64) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_tile: dtype must be complex128, complex64 or float64");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::syncdata_tile(device, p, rx, tx, rx_out, tx_out, &err);
-    return rc ? set_err(rc, "ssf_sync_tile: " + err) : SSF_OK;
+    return engine_call("ssf_sync_tile", device, [&](std::string *err) { return ssf::syncdata_tile(device, p, rx, tx, rx_out, tx_out, err); });
 }
 
 int ssf_sync_extract(int device, int64_t n, int32_t nModes, int64_t n_out, int32_t out_dtype, int32_t normalize, const void *x, void *out,
@@ -1065,19 +994,15 @@ int ssf_sync_extract(int device, int64_t n, int32_t nModes, int64_t n_out, int32
     if (nModes < 1 || nModes > 8) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_extract: nModes must be 1 .. 8");
     if (n < 1 || n > (1LL << 31) || n_out < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_extract: 1 <= n <= 2^31 and n_out >= 1");
     if (out_dtype != SSF_M_C128 && out_dtype != SSF_M_F64) return set_err(SSF_ERR_BAD_ARG, "ssf_sync_extract: out_dtype must be complex128 or float64");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::syncdata_extract(device, n, nModes, n_out, out_dtype, normalize != 0, x, out, kept, &err);
-    return rc ? set_err(rc, "ssf_sync_extract: " + err) : SSF_OK;
+    return engine_call("ssf_sync_extract", device, [&](std::string *err) {
+        return ssf::syncdata_extract(device, n, nModes, n_out, out_dtype, normalize != 0, x, out, kept, err);
+    });
 }
 
 int ssf_real_part(int device, int64_t count, const void *x, void *out) {
     if (!x || !out) return set_err(SSF_ERR_BAD_ARG, "ssf_real_part: NULL argument");
     if (count < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_real_part: count must be at least 1");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::syncdata_real_part(device, count, x, out, &err);
-    return rc ? set_err(rc, "ssf_real_part: " + err) : SSF_OK;
+    return engine_call("ssf_real_part", device, [&](std::string *err) { return ssf::syncdata_real_part(device, count, x, out, err); });
 }
 
 int ssf_copy_columns(int device, int64_t n, int32_t width, int32_t src_cols, int32_t src_first, int32_t dst_cols, int32_t dst_first, const void *src,
@@ -1087,10 +1012,9 @@ int ssf_copy_columns(int device, int64_t n, int32_t width, int32_t src_cols, int
         return set_err(SSF_ERR_BAD_ARG, "ssf_copy_columns: n >= 1 and the block of columns inside both arrays");
     if (src == dst) return set_err(SSF_ERR_BAD_ARG, "ssf_copy_columns: src and dst must be different arrays");
     if (!ssf::on_device(src) || !ssf::on_device(dst)) return set_err(SSF_ERR_BAD_ARG, "ssf_copy_columns: src and dst are device arrays");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::syncdata_copy_columns(device, n, width, src_cols, src_first, dst_cols, dst_first, src, dst, &err);
-    return rc ? set_err(rc, "ssf_copy_columns: " + err) : SSF_OK;
+    return engine_call("ssf_copy_columns", device, [&](std::string *err) {
+        return ssf::syncdata_copy_columns(device, n, width, src_cols, src_first, dst_cols, dst_first, src, dst, err);
+    });
 }
 
 int ssf_moving_average(int device, int64_t n, int32_t cols, int32_t N, int32_t dtype, const void *x, void *out) {
@@ -1098,19 +1022,13 @@ int ssf_moving_average(int device, int64_t n, int32_t cols, int32_t N, int32_t d
     if (N < 2 || N > 2048) return set_err(SSF_ERR_BAD_ARG, "ssf_moving_average: N must be 2 .. 2048");
     if (n < 1 || cols < 1 || cols > 65535) return set_err(SSF_ERR_BAD_ARG, "ssf_moving_average: n >= 1 and 1 <= cols <= 65535");
     if (dtype != SSF_M_C128 && dtype != SSF_M_C64 && dtype != SSF_M_F64) return set_err(SSF_ERR_BAD_ARG, "ssf_moving_average: dtype must be complex128, complex64 or float64");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::syncdata_moving_average(device, n, cols, N, dtype, x, out, &err);
-    return rc ? set_err(rc, "ssf_moving_average: " + err) : SSF_OK;
+    return engine_call("ssf_moving_average", device, [&](std::string *err) { return ssf::syncdata_moving_average(device, n, cols, N, dtype, x, out, err); });
 }
 
 int ssf_bert(int device, int64_t n, const void *irx, const void *bits, double *scal_out) {
     if (!irx || !bits || !scal_out) return set_err(SSF_ERR_BAD_ARG, "ssf_bert: NULL argument");
     if (n < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_bert: n must be at least 1");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::syncdata_bert(device, n, irx, bits, scal_out, &err);
-    return rc ? set_err(rc, "ssf_bert: " + err) : SSF_OK;
+    return engine_call("ssf_bert", device, [&](std::string *err) { return ssf::syncdata_bert(device, n, irx, bits, scal_out, err); });
 }
 
 // ---- soft-decision FEC (engine_fec.hip): every check comes before the first allocation, upload or launch
@@ -1125,10 +1043,7 @@ int ssf_calc_llr(int device, int64_t n, int32_t dtype, int32_t M, double sigma2,
     while ((1 << b) < M) ++b;
     for (int i = 0; i < M * b; ++i)
         if (bitmap[i] != 0 && bitmap[i] != 1) return set_err(SSF_ERR_BAD_ARG, "ssf_calc_llr: bitmap must hold 0 and 1 only");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::fec_calc_llr(device, n, dtype, M, sigma2, const_tab, bitmap, px, x, llr_out, &err);
-    return rc ? set_err(rc, "ssf_calc_llr: " + err) : SSF_OK;
+    return engine_call("ssf_calc_llr", device, [&](std::string *err) { return ssf::fec_calc_llr(device, n, dtype, M, sigma2, const_tab, bitmap, px, x, llr_out, err); });
 }
 
 // the kernels index with these arrays unchecked: nothing that could send them out of bounds, or two threads to one edge, gets in
@@ -1169,17 +1084,14 @@ int ssf_ldpc_graph_create(int device, int32_t m, int32_t n, int32_t E, const int
     int max_dc = 0;
     if (const char *msg = ldpc_graph_bad(m, n, E, check_offsets, edge_var, var_offsets, var_edge_indices, &max_dc))
         return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ldpc_graph_create: ") + msg);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::fec_graph_create(device, m, n, E, check_offsets, edge_var, var_offsets, var_edge_indices, max_dc, out, &err);
-    return rc ? set_err(rc, "ssf_ldpc_graph_create: " + err) : SSF_OK;
+    return engine_call("ssf_ldpc_graph_create", device, [&](std::string *err) {
+        return ssf::fec_graph_create(device, m, n, E, check_offsets, edge_var, var_offsets, var_edge_indices, max_dc, out, err);
+    });
 }
 
 int ssf_ldpc_graph_destroy(ssf_ldpc_graph *graph) {
     if (!graph) return SSF_OK;
-    std::string err;
-    int rc = ssf::fec_graph_destroy(graph, &err);
-    return rc ? set_err(rc, "ssf_ldpc_graph_destroy: " + err) : SSF_OK;
+    return engine_result("ssf_ldpc_graph_destroy", [&](std::string *err) { return ssf::fec_graph_destroy(graph, err); });
 }
 
 int ssf_ldpc_decode(int device, const ssf_ldpc_graph *graph, const ssf_ldpc_params *p, const void *llr_in, void *llr_out,
@@ -1196,10 +1108,9 @@ int ssf_ldpc_decode(int device, const ssf_ldpc_graph *graph, const ssf_ldpc_para
     else if (p->sync_every < 0) msg = "sync_every must not be negative";
     else if (device != graph->device) msg = "the graph lives on another device";
     if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ldpc_decode: ") + msg);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::fec_decode(device, graph, p, llr_in, llr_out, bits_out, fail_out, iter_out, &err);
-    return rc ? set_err(rc, "ssf_ldpc_decode: " + err) : SSF_OK;
+    return engine_call("ssf_ldpc_decode", device, [&](std::string *err) {
+        return ssf::fec_decode(device, graph, p, llr_in, llr_out, bits_out, fail_out, iter_out, err);
+    });
 }
 
 // ---- LDPC encoding and Gray mapping (engine_enc.hip): the kernels index with the CSR unchecked, so nothing out of range gets in
@@ -1229,17 +1140,12 @@ int ssf_ldpc_encoder_create(int device, const ssf_ldpc_encoder_desc *desc, const
     *out = nullptr;
     if (const char *msg = encoder_bad(desc, block1, block2, indptr, indices))
         return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ldpc_encoder_create: ") + msg);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::enc_create(device, desc, block1, block2, indptr, indices, out, &err);
-    return rc ? set_err(rc, "ssf_ldpc_encoder_create: " + err) : SSF_OK;
+    return engine_call("ssf_ldpc_encoder_create", device, [&](std::string *err) { return ssf::enc_create(device, desc, block1, block2, indptr, indices, out, err); });
 }
 
 int ssf_ldpc_encoder_destroy(ssf_ldpc_encoder *encoder) {
     if (!encoder) return SSF_OK;
-    std::string err;
-    int rc = ssf::enc_destroy(encoder, &err);
-    return rc ? set_err(rc, "ssf_ldpc_encoder_destroy: " + err) : SSF_OK;
+    return engine_result("ssf_ldpc_encoder_destroy", [&](std::string *err) { return ssf::enc_destroy(encoder, err); });
 }
 
 int ssf_ldpc_encode(int device, const ssf_ldpc_encoder *encoder, const ssf_ldpc_encode_params *p, const void *bits_in,
@@ -1251,19 +1157,13 @@ int ssf_ldpc_encode(int device, const ssf_ldpc_encoder *encoder, const ssf_ldpc_
     else if (p->n < 1 || p->n > full) msg = "n must be 1 .. the codeword's length";
     else if (device != encoder->device) msg = "the encoder lives on another device";
     if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ldpc_encode: ") + msg);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::enc_encode(device, encoder, p, bits_in, codewords_out, &err);
-    return rc ? set_err(rc, "ssf_ldpc_encode: " + err) : SSF_OK;
+    return engine_call("ssf_ldpc_encode", device, [&](std::string *err) { return ssf::enc_encode(device, encoder, p, bits_in, codewords_out, err); });
 }
 
 int ssf_modulate(int device, int64_t nsymb, int32_t M, const double *const_tab, const void *bits, void *symb_out) {
     if (!const_tab || !bits || !symb_out || nsymb < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate: bad argument");
     if (M < 2 || M > 1024 || (M & (M - 1))) return set_err(SSF_ERR_BAD_ARG, "ssf_modulate: M must be a power of two, 2 .. 1024");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::enc_modulate(device, nsymb, M, const_tab, bits, symb_out, &err);
-    return rc ? set_err(rc, "ssf_modulate: " + err) : SSF_OK;
+    return engine_call("ssf_modulate", device, [&](std::string *err) { return ssf::enc_modulate(device, nsymb, M, const_tab, bits, symb_out, err); });
 }
 
 // ---- OFDM (engine_ofdm.hip): the kernels index with the carrier tables unchecked, so nothing out of range gets in
@@ -1292,10 +1192,7 @@ int ssf_ofdm_modulate(int device, const ssf_ofdm_params *p, const int32_t *src_m
             msg = "src_map holds a code that names no source";
     }
     if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ofdm_modulate: ") + msg);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::ofdm_modulate(device, p, src_map, symb, out, &err);
-    return rc ? set_err(rc, "ssf_ofdm_modulate: " + err) : SSF_OK;
+    return engine_call("ssf_ofdm_modulate", device, [&](std::string *err) { return ssf::ofdm_modulate(device, p, src_map, symb, out, err); });
 }
 
 int ssf_ofdm_demodulate(int device, const ssf_ofdm_params *p, const int32_t *bin_carrier, const int32_t *data_carriers,
@@ -1313,10 +1210,9 @@ int ssf_ofdm_demodulate(int device, const ssf_ofdm_params *p, const int32_t *bin
     for (int c = 0; !msg && p->Np > 0 && c < p->Ns; ++c)
         if (pilot_hi[c] < 1 || pilot_hi[c] >= p->Np) msg = "pilot_hi holds a segment outside 1 .. Np - 1";
     if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_ofdm_demodulate: ") + msg);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::ofdm_demodulate(device, p, bin_carrier, data_carriers, pilot_carriers, pilot_hi, sig, symb_out, H_out, &err);
-    return rc ? set_err(rc, "ssf_ofdm_demodulate: " + err) : SSF_OK;
+    return engine_call("ssf_ofdm_demodulate", device, [&](std::string *err) {
+        return ssf::ofdm_demodulate(device, p, bin_carrier, data_carriers, pilot_carriers, pilot_hi, sig, symb_out, H_out, err);
+    });
 }
 
 // ---- perturbation model (engine_nlin.hip): the kernels index LDS and the symbols with m and n unchecked, so nothing out of range gets in
@@ -1354,10 +1250,9 @@ int ssf_pert_nlin(int device, const ssf_nlin_params *p, const int32_t *pass, con
     for (int k = 0; !msg && k < p->nphase; ++k)
         if (phase_m[k] < -L || phase_m[k] > L) msg = "phase_m holds an m outside -L .. L";
     if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_pert_nlin: ") + msg);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::nlin_run(device, p, pass, coef, nidx, phase_m, phase_c, x, y, out0, out1, out2, out3, &err);
-    return rc ? set_err(rc, "ssf_pert_nlin: " + err) : SSF_OK;
+    return engine_call("ssf_pert_nlin", device, [&](std::string *err) {
+        return ssf::nlin_run(device, p, pass, coef, nidx, phase_m, phase_c, x, y, out0, out1, out2, out3, err);
+    });
 }
 
 // ---- the sampling clock (engine_clock.hip): every check comes before the first allocation, upload or launch
@@ -1379,43 +1274,28 @@ int ssf_clock_interp(int device, const ssf_clock_params *p, const void *x, const
     else if (p->quantize && clock_bad_table(p->qmin, p->qdelta, p->qlevels)) msg = "bad quantizer table";
     if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_clock_interp: ") + msg);
     if (p->n_out == 0) return SSF_OK;
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::clock_interp(device, p, x, t_re, t_im, out, &err);
-    return rc ? set_err(rc, "ssf_clock_interp: " + err) : SSF_OK;
+    return engine_call("ssf_clock_interp", device, [&](std::string *err) { return ssf::clock_interp(device, p, x, t_re, t_im, out, err); });
 }
 
 int ssf_quantize(int device, int64_t count, int32_t dtype, double qmin, double qdelta, int64_t qlevels, const void *x, double *out) {
     if (!x || !out || count < 1 || clock_bad_dtype(dtype) || clock_bad_table(qmin, qdelta, qlevels))
         return set_err(SSF_ERR_BAD_ARG, "ssf_quantize: bad argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::clock_quantize(device, count, dtype, qmin, qdelta, qlevels, x, out, &err);
-    return rc ? set_err(rc, "ssf_quantize: " + err) : SSF_OK;
+    return engine_call("ssf_quantize", device, [&](std::string *err) { return ssf::clock_quantize(device, count, dtype, qmin, qdelta, qlevels, x, out, err); });
 }
 
 int ssf_clip(int device, int64_t count, int32_t dtype, double lo, double hi, const void *x, void *out) {
     if (!x || !out || count < 1 || clock_bad_dtype(dtype) || !(lo <= hi)) return set_err(SSF_ERR_BAD_ARG, "ssf_clip: bad argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::clock_clip(device, count, dtype, lo, hi, x, out, &err);
-    return rc ? set_err(rc, "ssf_clip: " + err) : SSF_OK;
+    return engine_call("ssf_clip", device, [&](std::string *err) { return ssf::clock_clip(device, count, dtype, lo, hi, x, out, err); });
 }
 
 int ssf_minmax(int device, int64_t count, int32_t dtype, const void *x, double *out2) {
     if (!x || !out2 || count < 1 || clock_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_minmax: bad argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::clock_minmax(device, count, dtype, x, out2, &err);
-    return rc ? set_err(rc, "ssf_minmax: " + err) : SSF_OK;
+    return engine_call("ssf_minmax", device, [&](std::string *err) { return ssf::clock_minmax(device, count, dtype, x, out2, err); });
 }
 
 int ssf_clock_scale_add(int device, int64_t count, double scale, int32_t has_scale, const double *x, const double *noise, double *out) {
     if (!x || !out || count < 1) return set_err(SSF_ERR_BAD_ARG, "ssf_clock_scale_add: bad argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::clock_scale_add(device, count, scale, has_scale, x, noise, out, &err);
-    return rc ? set_err(rc, "ssf_clock_scale_add: " + err) : SSF_OK;
+    return engine_call("ssf_clock_scale_add", device, [&](std::string *err) { return ssf::clock_scale_add(device, count, scale, has_scale, x, noise, out, err); });
 }
 
 int ssf_gardner(int device, const ssf_gardner_params *p, const void *x, void *sig_out, double *t_out, int64_t *last_n) {
@@ -1427,18 +1307,12 @@ int ssf_gardner(int device, const ssf_gardner_params *p, const void *x, void *si
     else if (p->nModes < 1 || p->nModes > 65535) msg = "nModes must be 1 .. 65535";
     else if (!std::isfinite(p->kp) || !std::isfinite(p->ki)) msg = "kp and ki must be finite";
     if (msg) return set_err(SSF_ERR_BAD_ARG, std::string("ssf_gardner: ") + msg);
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::clock_gardner(device, p, x, sig_out, t_out, last_n, &err);
-    return rc ? set_err(rc, "ssf_gardner: " + err) : SSF_OK;
+    return engine_call("ssf_gardner", device, [&](std::string *err) { return ssf::clock_gardner(device, p, x, sig_out, t_out, last_n, err); });
 }
 
 int ssf_clock_drift(int device, int64_t n, int32_t ncols, int32_t per_column, const double *t, double *ppm_out) {
     if (!t || !ppm_out || n < 1 || ncols < 1 || ncols > 65535 || n > (1LL << 40)) return set_err(SSF_ERR_BAD_ARG, "ssf_clock_drift: bad argument");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::clock_drift(device, n, ncols, per_column, t, ppm_out, &err);
-    return rc ? set_err(rc, "ssf_clock_drift: " + err) : SSF_OK;
+    return engine_call("ssf_clock_drift", device, [&](std::string *err) { return ssf::clock_drift(device, n, ncols, per_column, t, ppm_out, err); });
 }
 
 // ---- the array layer of DeviceArray (engine_array.hip): every check comes before the first allocation or launch
@@ -1501,10 +1375,7 @@ int ssf_array_copy(int device, const ssf_array_desc *src_desc, const void *src, 
     }
     if (src == dst) return set_err(SSF_ERR_BAD_ARG, "ssf_array_copy: in place is not supported");
     if (count == 0) return SSF_OK;
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::array_copy(device, src_desc, src, dst_desc, dst, &err);
-    return rc ? set_err(rc, "ssf_array_copy: " + err) : SSF_OK;
+    return engine_call("ssf_array_copy", device, [&](std::string *err) { return ssf::array_copy(device, src_desc, src, dst_desc, dst, err); });
 }
 
 int ssf_array_take(int device, int64_t n_src, int64_t n_idx, int64_t inner, int32_t itemsize, int32_t idx_itemsize, const void *idx,
@@ -1514,10 +1385,9 @@ int ssf_array_take(int device, int64_t n_src, int64_t n_idx, int64_t inner, int3
         return set_err(SSF_ERR_BAD_ARG, "ssf_array_take: bad sizes");
     if (array_bad_itemsize(itemsize) || (idx_itemsize != 4 && idx_itemsize != 8)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_take: bad itemsize");
     if (n_idx == 0 || inner == 0) return SSF_OK;
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::array_take(device, n_src, n_idx, inner, itemsize, idx_itemsize, idx, src, dst, &err);
-    return rc ? set_err(rc, "ssf_array_take: " + err) : SSF_OK;
+    return engine_call("ssf_array_take", device, [&](std::string *err) {
+        return ssf::array_take(device, n_src, n_idx, inner, itemsize, idx_itemsize, idx, src, dst, err);
+    });
 }
 
 int ssf_array_transpose(int device, int64_t rows, int64_t cols, int32_t itemsize, const void *src, void *dst) {
@@ -1526,20 +1396,15 @@ int ssf_array_transpose(int device, int64_t rows, int64_t cols, int32_t itemsize
         return set_err(SSF_ERR_BAD_ARG, "ssf_array_transpose: bad sizes");
     if (((rows + 31) / 32) * ((cols + 31) / 32) > 0x7fffffffLL) return set_err(SSF_ERR_UNSUPPORTED, "ssf_array_transpose: too many tiles");
     if (rows == 0 || cols == 0) return SSF_OK;
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::array_transpose(device, rows, cols, itemsize, src, dst, &err);
-    return rc ? set_err(rc, "ssf_array_transpose: " + err) : SSF_OK;
+    return engine_call("ssf_array_transpose", device, [&](std::string *err) { return ssf::array_transpose(device, rows, cols, itemsize, src, dst, err); });
 }
 
 int ssf_array_fill(int device, int64_t count, int32_t itemsize, const void *value, void *dst) {
     if (!value || !dst || count < 0 || count > kArrayMax || array_bad_itemsize(itemsize)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_fill: bad argument");
     if (count == 0) return SSF_OK;
-    if (int rc = rx_check_device(device)) return rc;
+    if (int rc = check_device(device)) return rc;
     if (ssf::on_device(value)) return set_err(SSF_ERR_BAD_ARG, "ssf_array_fill: the value is host memory");
-    std::string err;
-    int rc = ssf::array_fill(device, count, itemsize, value, dst, &err);
-    return rc ? set_err(rc, "ssf_array_fill: " + err) : SSF_OK;
+    return engine_result("ssf_array_fill", [&](std::string *err) { return ssf::array_fill(device, count, itemsize, value, dst, err); });
 }
 
 int ssf_array_binary(int device, const ssf_array_binary_params *p, const void *a, const void *b, void *out) {
@@ -1555,10 +1420,7 @@ int ssf_array_binary(int device, const ssf_array_binary_params *p, const void *a
         return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: inner must divide count");
     if (a == out || b == out) return set_err(SSF_ERR_BAD_ARG, "ssf_array_binary: in place is not supported");
     if (p->count == 0) return SSF_OK;
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::array_binary(device, p, a, b, out, &err);
-    return rc ? set_err(rc, "ssf_array_binary: " + err) : SSF_OK;
+    return engine_call("ssf_array_binary", device, [&](std::string *err) { return ssf::array_binary(device, p, a, b, out, err); });
 }
 
 int ssf_array_unary(int device, int32_t op, int32_t in_dtype, int32_t out_dtype, int64_t count, const void *x, void *out) {
@@ -1571,10 +1433,7 @@ int ssf_array_unary(int device, int32_t op, int32_t in_dtype, int32_t out_dtype,
     if (real_result ? out_c : (op == SSF_ARRAY_CONVERT ? (in_c && !out_c) : in_c != out_c))
         return set_err(SSF_ERR_BAD_ARG, "ssf_array_unary: the result dtype does not fit the operation");
     if (count == 0) return SSF_OK;
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::array_unary(device, op, in_dtype, out_dtype, count, x, out, &err);
-    return rc ? set_err(rc, "ssf_array_unary: " + err) : SSF_OK;
+    return engine_call("ssf_array_unary", device, [&](std::string *err) { return ssf::array_unary(device, op, in_dtype, out_dtype, count, x, out, err); });
 }
 
 int ssf_array_reduce(int device, int32_t op, int32_t dtype, int64_t rows, int32_t cols, const double *center, const void *x, double *out,
@@ -1585,10 +1444,9 @@ int ssf_array_reduce(int device, int32_t op, int32_t dtype, int64_t rows, int32_
     if (op == SSF_ARRAY_SUMSQDEV && !center) return set_err(SSF_ERR_BAD_ARG, "ssf_array_reduce: the squared deviations need a centre");
     if ((op == SSF_ARRAY_MIN || op == SSF_ARRAY_MAX) && (!arg_out || dtype <= SSF_M_C64))
         return set_err(SSF_ERR_BAD_ARG, "ssf_array_reduce: min and max are for real arrays and need arg_out");
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::array_reduce(device, op, dtype, rows, cols, op == SSF_ARRAY_SUMSQDEV ? center : nullptr, x, out, arg_out, &err);
-    return rc ? set_err(rc, "ssf_array_reduce: " + err) : SSF_OK;
+    return engine_call("ssf_array_reduce", device, [&](std::string *err) {
+        return ssf::array_reduce(device, op, dtype, rows, cols, op == SSF_ARRAY_SUMSQDEV ? center : nullptr, x, out, arg_out, err);
+    });
 }
 
 int ssf_freq_shift(int device, int64_t n, int32_t ncols, int32_t dtype, double deltaF, double Fs, const void *x, void *out) {
@@ -1596,10 +1454,7 @@ int ssf_freq_shift(int device, int64_t n, int32_t ncols, int32_t dtype, double d
     if (n < 0 || ncols < 1 || n > kArrayMax / ncols || array_bad_dtype(dtype)) return set_err(SSF_ERR_BAD_ARG, "ssf_freq_shift: bad sizes or dtype");
     if (!std::isfinite(deltaF) || !std::isfinite(Fs) || Fs == 0) return set_err(SSF_ERR_BAD_ARG, "ssf_freq_shift: deltaF must be finite, Fs finite and non-zero");
     if (n == 0) return SSF_OK;
-    if (int rc = rx_check_device(device)) return rc;
-    std::string err;
-    int rc = ssf::array_freq_shift(device, n, ncols, dtype, deltaF, Fs, x, out, &err);
-    return rc ? set_err(rc, "ssf_freq_shift: " + err) : SSF_OK;
+    return engine_call("ssf_freq_shift", device, [&](std::string *err) { return ssf::array_freq_shift(device, n, ncols, dtype, deltaF, Fs, x, out, err); });
 }
 
 }  // extern "C"
